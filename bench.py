@@ -11,8 +11,16 @@ the device output arena; the PCIe-inclusive rates are reported separately as
 `ops_per_sec_with_d2h` (full records, pipelined payload copy) and
 `ops_per_sec_with_d2h_keys_only` (etcd3 KeysOnly semantics — key+mod-rev
 only; the reference's shim ignores that flag, so this is an extension and is
-never `value`). The default run also times the configs[2] compaction sweep
-and the 10k-watcher fan-out leg (configs[4] shape at N=1).
+never `value`).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what `value` needs:
+load the keyspace, warm up, time the N steps, print the result line. `--full`
+adds every other leg after the timed steps, as before: the PCIe-inclusive
+rates, the configs[2] compaction sweep, the 10k-watcher fan-out leg
+(configs[4] shape at N=1), the cross-shard Range leg at N>1, the host probe
+and the CPU baselines. `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (see dump_outputs). The step sequence is a pure
+function of the arguments, so two builds can be compared output for output.
 
 Multi-GPU (--gpus N via torch.distributed.run): keys shard by namespace hash,
 one store per GPU; the query stream routes by namespace; weak scaling
@@ -38,6 +46,7 @@ VAL_LEN = 512
 LIMIT = 500
 OPS_PER_STEP = 1000
 RANGE_SHARE = 0.9
+MAX_PRE_STEPS = 256
 
 
 def log(rank, *a):
@@ -47,15 +56,17 @@ def log(rank, *a):
 
 def make_keys(nns, per_ns):
     namespaces = [b"/registry/pods/ns-%04d" % i for i in range(nns)]
-    keys = []
-    for ns in namespaces:
-        for j in range(per_ns):
-            keys.append(ns + b"/pod-%06d" % j)
+    pods = [b"/pod-%06d" % j for j in range(per_ns)]
+    keys = [ns + pod for ns in namespaces for pod in pods]
     return namespaces, keys
 
 
 def build_store(store, namespaces, keys, rng, extra_revs, tomb_frac, my_ns=None):
-    """Load the synthetic keyspace through the normal write path."""
+    """Load the synthetic keyspace through the normal write path. Returns the
+    loaded keys and, per key index, its latest revision (uint64; 0 once the
+    key is tombstoned)."""
+    from concurrent.futures import ThreadPoolExecutor
+
     t_phase = time.time()
 
     def phase(name):
@@ -71,24 +82,38 @@ def build_store(store, namespaces, keys, rng, extra_revs, tomb_frac, my_ns=None)
     # chunked load (1M keys per call) bounds host memory at 10M-key scale
     f = store._f("bulk_create")
     CH = 1 << 20
-    for c0 in range(0, n, CH):
+
+    def gen_chunk(c0):
         ck = sel[c0:c0 + CH]
         m = len(ck)
-        vals = rng.integers(0, 256, size=m * VAL_LEN, dtype=np.uint8).tobytes()
-        klens = np.array([len(k) for k in ck], dtype=np.uint32).tobytes()
-        vlens = np.full(m, VAL_LEN, dtype=np.uint32).tobytes()
-        kblob = b"".join(ck)
-        rc = f(ctypes.c_void_p(store.h), kblob, klens, vals, vlens,
-               ctypes.c_size_t(m))
-        assert rc == 0, "bulk_create failed"
+        # full-range uint32 draws give the same byte stream (and leave the
+        # generator in the same state) as one uint8 draw per byte, faster
+        vals = rng.integers(0, 1 << 32, size=m * VAL_LEN // 4, dtype=np.uint32)
+        klens = np.fromiter(map(len, ck), dtype=np.uint32, count=m)
+        vlens = np.full(m, VAL_LEN, dtype=np.uint32)
+        return m, b"".join(ck), klens, vals, vlens
+
+    base = store.current_rev()
+    # the next chunk is generated while the store ingests the current one;
+    # only the worker draws from rng here, so the stream order is unchanged
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        nxt = pool.submit(gen_chunk, 0) if n else None
+        for c0 in range(0, n, CH):
+            m, kblob, klens, vals, vlens = nxt.result()
+            nxt = pool.submit(gen_chunk, c0 + CH) if c0 + CH < n else None
+            rc = f(ctypes.c_void_p(store.h), kblob,
+                   ctypes.c_void_p(klens.ctypes.data),
+                   ctypes.c_void_p(vals.ctypes.data),
+                   ctypes.c_void_p(vlens.ctypes.data), ctypes.c_size_t(m))
+            assert rc == 0, "bulk_create failed"
     phase("bulk_create")
-    revs = {k: None for k in sel}  # latest rev per key tracked client-side
-    base = store.current_rev() - n
-    for i, k in enumerate(sel):
-        revs[k] = base + i + 1
+    # latest rev per key index tracked client-side: creates take consecutive
+    # revisions in load order
+    assert store.current_rev() == base + n, "bulk_create revision drift"
+    revs = np.arange(base + 1, base + n + 1, dtype=np.uint64)
     # extra revisions, zipf(1.1) — batched through the C txn path
     if extra_revs and n:
-        zs = (rng.zipf(1.1, size=extra_revs) - 1) % n
+        zs = ((rng.zipf(1.1, size=extra_revs) - 1) % n).tolist()
         vbuf = rng.integers(0, 256, size=VAL_LEN, dtype=np.uint8).tobytes()
         done = 0
         batch = 8192
@@ -96,13 +121,12 @@ def build_store(store, namespaces, keys, rng, extra_revs, tomb_frac, my_ns=None)
             # unique keys per batch (revs must chain between batches)
             uniq, seen = [], set()
             while done < extra_revs and len(uniq) < batch:
-                k = sel[int(zs[done])]
-                if k not in seen:
-                    seen.add(k)
-                    uniq.append(k)
+                ki = zs[done]
+                if ki not in seen:
+                    seen.add(ki)
+                    uniq.append(ki)
                 done += 1
-            txn_batch(store, [(k, revs[k], vbuf) for k in uniq], revs,
-                      must_succeed=True)
+            txn_batch(store, sel, uniq, revs, vbuf, must_succeed=True)
         phase("extra revisions")
     # tombstones
     if tomb_frac and n:
@@ -111,19 +135,19 @@ def build_store(store, namespaces, keys, rng, extra_revs, tomb_frac, my_ns=None)
         fdel = store._f("bench_del")
         batch = 8192
         for b0 in range(0, nt, batch):
-            ks = [sel[int(i)] for i in idx[b0:b0 + batch]]
+            ki = idx[b0:b0 + batch]
             parts = []
-            for k in ks:
-                parts.append(struct.pack("<IQ", len(k), revs[k]))
+            for i, pr in zip(ki.tolist(), revs[ki].tolist()):
+                k = sel[i]
+                parts.append(struct.pack("<IQ", len(k), pr))
                 parts.append(k)
-            out = np.empty(len(ks), dtype=np.uint64)
+            out = np.empty(len(ki), dtype=np.uint64)
             rc = fdel(ctypes.c_void_p(store.h), b"".join(parts),
-                      ctypes.c_size_t(len(ks)),
+                      ctypes.c_size_t(len(ki)),
                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
             assert rc == 0
-            for k, nr in zip(ks, out):
-                assert nr != 0
-                revs[k] = None
+            assert out.all()
+            revs[ki] = 0
         phase("tombstones")
     store._f("flush")(ctypes.c_void_p(store.h))
     phase("final fold")
@@ -149,24 +173,27 @@ def gen_step_queries(rng, namespaces, cur_rev, n):
     return out
 
 
-def txn_batch(store, ops, revs, must_succeed=False):
-    """ops: [(key, prev_rev, val)] with unique keys; updates revs in place."""
+def txn_batch(store, keys, idx, revs, val, must_succeed=False):
+    """One conditional update of `val` per key index in idx (unique), each
+    against its tracked revision; updates revs in place."""
+    ia = np.asarray(idx, dtype=np.int64)
     parts = []
-    for k, pr, v in ops:
-        parts.append(struct.pack("<IQI", len(k), pr, len(v)))
+    for i, pr in zip(ia.tolist(), revs[ia].tolist()):
+        k = keys[i]
+        parts.append(struct.pack("<IQI", len(k), pr, len(val)))
         parts.append(k)
-        parts.append(v)
+        parts.append(val)
     blob = b"".join(parts)
-    out = np.empty(len(ops), dtype=np.uint64)
+    out = np.empty(len(ia), dtype=np.uint64)
     rc = store._f("bench_txn")(ctypes.c_void_p(store.h), blob,
-                               ctypes.c_size_t(len(ops)),
+                               ctypes.c_size_t(len(ia)),
                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
     assert rc == 0
-    for (k, _pr, _v), nr in zip(ops, out):
-        if nr != 0:
-            revs[k] = int(nr)
-        elif must_succeed:
-            raise AssertionError(f"seed update failed for {k!r}")
+    ok = out != 0
+    if must_succeed and not ok.all():
+        raise AssertionError(
+            f"seed update failed for {keys[int(ia[~ok][0])]!r}")
+    revs[ia[ok]] = out[ok]
 
 
 def bench_range_call(store, blob, nq, d2h):
@@ -196,17 +223,16 @@ def perf(store):
     return json.loads(buf.value.decode())
 
 
-def run_txns(store, live_keys, revs, rng, n):
+def run_txns(store, keys, live, revs, rng, n):
     vbuf = rng.integers(0, 256, size=VAL_LEN, dtype=np.uint8).tobytes()
-    ops, seen = [], set()
-    while len(ops) < n:
-        k = live_keys[int(rng.integers(len(live_keys)))]
-        pr = revs.get(k)
-        if pr is None or k in seen:
+    idx, seen = [], set()
+    while len(idx) < n:
+        ki = int(live[int(rng.integers(len(live)))])
+        if revs[ki] == 0 or ki in seen:
             continue
-        seen.add(k)
-        ops.append((k, pr, vbuf))
-    txn_batch(store, ops, revs)
+        seen.add(ki)
+        idx.append(ki)
+    txn_batch(store, keys, idx, revs, vbuf)
 
 
 def cross_shard_leg_wrapper(store, dist, pg, rank, world, all_namespaces):
@@ -414,7 +440,7 @@ def cpu_baseline_leg(namespaces, keys, sample_qs):
     }
 
 
-def watch_leg(store, namespaces, live_keys, revs, rng, n_watchers, n_events):
+def watch_leg(store, namespaces, keys, live, revs, rng, n_watchers, n_events):
     """configs[4]-shaped fan-out: n_watchers live watchers, n_events writes.
     `delivered` counts events landed in watcher queues (bitmap references —
     the same cost model as the reference's shared-batch-pointer fan-out,
@@ -432,7 +458,7 @@ def watch_leg(store, namespaces, live_keys, revs, rng, n_watchers, n_events):
         wids.append(wid)
     p0 = perf(store)
     t0 = time.time()
-    run_txns(store, live_keys, revs, rng, n_events)
+    run_txns(store, keys, live, revs, rng, n_events)
     # final pump via a poll
     store.watch_poll(wids[0])
     dt = time.time() - t0
@@ -458,6 +484,66 @@ def watch_leg(store, namespaces, live_keys, revs, rng, n_watchers, n_events):
     return delivered / dt if dt > 0 else 0.0, delivered, stats
 
 
+DUMP_SAMPLE_QUERIES = 8
+
+
+def dump_outputs(out_dir, store, queries, step_totals, txn_revs, suffix=""):
+    """Write what the last timed step computed as <out_dir>/<name>.npy.
+
+    What kb_bench_step hands its caller:
+      step_range_totals  float64 [steps]  Range rows reported by each timed
+                                          call (pipelined: step k reports the
+                                          batch launched by step k-1)
+      txn_revisions      float64 [ntx]    new revision of each conditional
+                                          update of the last step (0 = CAS
+                                          failed)
+    The Range records themselves stay in the device output arena, so the
+    last step's query batch is read back through the List API at the same
+    read revisions (snapshot-exact, so later writes do not change it):
+      range_counts       float64 [nq]         rows returned per query
+      range_more         float64 [nq]         the More flag per query
+      range_revisions    float64 [nq, LIMIT]  mod revision per row (0 pad)
+      range_crc32        float64 [nq, LIMIT]  crc32(key + value) per row
+      range_sample_values float32 [8, LIMIT, VAL_LEN]  value bytes of a
+                                          fixed seeded sample of 8 queries
+    About 16 MB at the default shape."""
+    import zlib
+
+    os.makedirs(out_dir, exist_ok=True)
+    nq = len(queries)
+    counts = np.zeros(nq, dtype=np.float64)
+    more = np.zeros(nq, dtype=np.float64)
+    rows_rev = np.zeros((nq, LIMIT), dtype=np.float64)
+    rows_crc = np.zeros((nq, LIMIT), dtype=np.float64)
+    ns = min(DUMP_SAMPLE_QUERIES, nq)
+    sample = sorted(np.random.default_rng(SEED).choice(nq, size=ns,
+                                                       replace=False).tolist())
+    values = np.zeros((ns, LIMIT, VAL_LEN), dtype=np.float32)
+    for qi, (s, e, rev, limit) in enumerate(queries):
+        r = store.list(s, e, rev, limit)
+        assert r.status == 0, f"dump read-back failed: status {r.status}"
+        counts[qi] = len(r.kvs)
+        more[qi] = float(r.more)
+        slot = sample.index(qi) if qi in sample else -1
+        for j, kv in enumerate(r.kvs[:LIMIT]):
+            rows_rev[qi, j] = kv.revision
+            rows_crc[qi, j] = zlib.crc32(kv.key + kv.value)
+            if slot >= 0:
+                v = np.frombuffer(kv.value[:VAL_LEN], dtype=np.uint8)
+                values[slot, j, :len(v)] = v
+    arrays = {
+        "step_range_totals": np.asarray(step_totals, dtype=np.float64),
+        "txn_revisions": np.asarray(txn_revs, dtype=np.float64),
+        "range_counts": counts,
+        "range_more": more,
+        "range_revisions": rows_rev,
+        "range_crc32": rows_crc,
+        "range_sample_values": values,
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -469,11 +555,24 @@ def main():
     ap.add_argument("--extra-revs", type=int, default=1000000)
     ap.add_argument("--watchers", type=int, default=10000)
     ap.add_argument("--watch-events", type=int, default=6000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg "
+                         "(PCIe-inclusive rates, compaction sweep, watch "
+                         "fan-out, cross-shard Range at N>1, host probe, CPU "
+                         "baselines) and add their keys to the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one "
+                         "computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--spin-up", type=float, default=2.0, metavar="SECONDS",
+                    help="sustained range-only load before the warmup steps, "
+                         "so the clocks reach steady boost (default 2.0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-compact-bench", action="store_true",
-                    help="skip the compaction-sweep leg (configs[2] shape; "
-                         "on by default)")
+                    help="with --full: skip the compaction-sweep leg "
+                         "(configs[2] shape)")
     args = ap.parse_args()
+    t_start = time.time()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -507,7 +606,15 @@ def main():
     os.environ.setdefault("KB_EVENT_LOG", "0")
 
     import kubebrain_amd
-    import torch
+
+    # torch is first needed at the barrier before the timed steps; importing
+    # it takes seconds, so it loads in the background while the store ingests
+    # the keyspace (the load sits in native code and does not hold the GIL)
+    import importlib
+    import threading
+    torch_import = threading.Thread(target=importlib.import_module,
+                                    args=("torch",), daemon=True)
+    torch_import.start()
 
     import zlib
     namespaces, keys = make_keys(args.nns, args.per_ns)
@@ -523,7 +630,7 @@ def main():
     sel, revs = build_store(store, namespaces, keys, rng,
                             args.extra_revs // world, 0.02,
                             my_ns if world > 1 else None)
-    live = [k for k in sel if revs[k] is not None]
+    live = np.flatnonzero(revs)  # key indices not tombstoned
     log(rank, f"[bench] loaded {len(sel)} keys in {time.time()-t0:.1f}s; "
               f"slab={perf(store)['slab_rows']} rows")
 
@@ -537,12 +644,15 @@ def main():
     # update the client map after each step.
     nq = int(OPS_PER_STEP * RANGE_SHARE)  # 900 ranges
     ntx = OPS_PER_STEP - nq               # 100 txns
-    n_pre = args.warmup + args.steps + max(2, args.steps // 8) + 2
+    # The stream is bounded, so that generating it stays a small fixed cost
+    # at any --steps: longer runs cycle through the pre-generated steps.
+    n_pre = min(args.warmup + args.steps + max(2, args.steps // 8) + 2,
+                MAX_PRE_STEPS)
     cur = store.current_rev()
-    pre_blobs = [pack_queries(gen_step_queries(qrng, my_ns_list, cur, nq))
-                 for _ in range(n_pre)]
+    pre_qs = [gen_step_queries(qrng, my_ns_list, cur, nq) for _ in range(n_pre)]
+    pre_blobs = [pack_queries(qs) for qs in pre_qs]
     vbuf = qrng.integers(0, 256, size=VAL_LEN, dtype=np.uint8).tobytes()
-    tx_keys, tx_blobs, seen_tx = [], [], set()
+    tx_idx, seen_tx = [], set()
     for _ in range(n_pre):
         ks, step_seen, attempts = [], set(), 0
         while len(ks) < ntx:
@@ -551,13 +661,14 @@ def main():
                 seen_tx.clear()  # small pools: reuse keys (stale prev-revs
                 # then CAS-fail, which is legitimate mix noise; the default
                 # 1M-key config never reuses)
-            k = live[int(qrng.integers(len(live)))]
-            if k in seen_tx or k in step_seen or revs.get(k) is None:
+            ki = int(live[int(qrng.integers(len(live)))])
+            if ki in seen_tx or ki in step_seen or revs[ki] == 0:
                 continue
-            seen_tx.add(k)
-            step_seen.add(k)
-            ks.append(k)
-        tx_keys.append(ks)
+            seen_tx.add(ki)
+            step_seen.add(ki)
+            ks.append(ki)
+        tx_idx.append(np.array(ks, dtype=np.int64))
+    tx_keys = [[sel[ki] for ki in ia.tolist()] for ia in tx_idx]
     fstep = store._f("bench_step")
     tx_out = np.empty(ntx, dtype=np.uint64)
     tx_out_ptr = tx_out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
@@ -565,36 +676,43 @@ def main():
 
     t_split = {"range_s": 0.0, "txn_s": 0.0}
 
-    def one_step(mode=0):
+    def one_step(mode=0, txns=True):
         # one call: range batch launched async, txn batch overlapped on the
         # host while the kernels are in flight (kb_bench_step). mode bit0 =
         # d2h (pipelined payload copy), bit1 = keys_only, bit2 = pipelined.
         # The txn blob is packed HERE, per step, from the tracked revisions:
         # pre-built blobs go stale once the key pool cycles and every CAS
         # then fails, silently dropping the write half of the 90/10 mix.
+        # txns=False sends the range batch alone and leaves the store as it
+        # was (the spin-up steps before warmup).
         i = step_i[0] % n_pre
         step_i[0] += 1
+        ia = tx_idx[i]
         parts = []
-        for k in tx_keys[i]:
-            parts.append(struct.pack("<IQI", len(k), revs[k], VAL_LEN))
-            parts.append(k)
-            parts.append(vbuf)
+        if txns:
+            for k, pr in zip(tx_keys[i], revs[ia].tolist()):
+                parts.append(struct.pack("<IQI", len(k), pr, VAL_LEN))
+                parts.append(k)
+                parts.append(vbuf)
         tx_blob = b"".join(parts)
         total = ctypes.c_ulonglong()
         secs = ctypes.c_double()
         rc = fstep(ctypes.c_void_p(store.h), pre_blobs[i], ctypes.c_size_t(nq),
-                   tx_blob, ctypes.c_size_t(ntx),
+                   tx_blob, ctypes.c_size_t(ntx if txns else 0),
                    ctypes.c_int(mode), tx_out_ptr,
                    ctypes.byref(total), ctypes.byref(secs))
         assert rc == 0
         t_split["range_s"] += secs.value
-        for k, nr in zip(tx_keys[i], tx_out):
-            if nr != 0:
-                revs[k] = int(nr)
+        if txns:
+            ok = tx_out != 0
+            revs[ia[ok]] = tx_out[ok]
         return total.value
 
     def drain():
         assert store._f("sync")(ctypes.c_void_p(store.h)) == 0
+
+    torch_import.join()
+    import torch
 
     def barrier():
         if dist:
@@ -602,23 +720,30 @@ def main():
         if torch.cuda.is_available():
             torch.cuda.synchronize()
 
-    # warmup: at least args.warmup steps AND >= 2s of sustained load, so the
-    # clock governor reaches steady boost before the timed region (short
-    # warmups showed ~2x run-to-run variance across boxes)
+    # warmup: args.warmup steps AND >= 2s (--spin-up) of sustained load, so
+    # the clock governor reaches steady boost before the timed region (short
+    # warmups showed ~2x run-to-run variance across hosts). The time-bound
+    # part comes first and sends range batches only: how many of them fit in
+    # 2s varies from run to run, and they must not move the store's
+    # revisions, or the timed steps' inputs would differ from run to run.
+    log(rank, f"[bench] setup done {time.time()-t_start:.1f}s after start")
     t0 = time.time()
-    wsteps = 0
-    while wsteps < args.warmup or time.time() - t0 < 2.0:
+    spin = 0
+    while time.time() - t0 < args.spin_up and spin < 10000:
+        one_step(mode=4, txns=False)
+        spin += 1
+    drain()
+    step_i[0] = 0  # warmup and timed steps always use the same stream
+    for _ in range(args.warmup):
         one_step(mode=4)  # pipelined: previous batch collected next step
-        wsteps += 1
-        if wsteps > 10000:
-            break
     drain()
     barrier()
     store._f("perf_reset")(ctypes.c_void_p(store.h))
     t_split["range_s"] = t_split["txn_s"] = 0.0
+    step_totals = []
     t0 = time.time()
     for _ in range(args.steps):
-        one_step(mode=4)
+        step_totals.append(one_step(mode=4))
     drain()  # finish the in-flight final batch inside the timed bracket
     barrier()
     elapsed = time.time() - t0
@@ -629,11 +754,97 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     p = perf(store)
+    log(rank, f"[bench] timed {args.steps} steps in {elapsed:.3f}s")
 
-    # one-off PCIe reference: pinned D2H bandwidth of this box (torch copy)
-    # box-health probe: host spin speed + GPU sclk, reported with every line
-    # (box-to-box variance on this pool reaches 3x; a slow `value` with a
-    # slow probe is the box, not the code)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, store,
+                     pre_qs[(step_i[0] - 1) % n_pre] if args.steps else [],
+                     step_totals, tx_out.copy() if args.steps else [],
+                     suffix=f"_rank{rank}" if world > 1 else "")
+        log(rank, f"[bench] outputs written to {args.dump_outputs}")
+
+    total_ops = OPS_PER_STEP * args.steps * world
+    value = total_ops / elapsed
+    # roofline over the range path (scan + winner gather), per SURVEY §8d's
+    # algorithmic bytes: 16B per row scanned (meta+rev, DESIGN.md §3.3) +
+    # gathered record bytes (key+value+header per winner)
+    rng_s = (p["scan_ms"] + p["gather_ms"]) / 1e3
+    alg_bytes = p["rows_scanned"] * 16 + p["bytes_gathered"]
+    achieved = alg_bytes / rng_s if rng_s > 0 else 0.0
+    peak = 8.0e12
+    roofline = {
+        "bound": "hbm",
+        "achieved": round(achieved / 1e9, 2),
+        "peak": peak / 1e9,
+        "unit": "GB/s",
+        "frac": round(achieved / peak, 4),
+        "traffic": None,  # filled below from the committed PMC sidecar
+        "kernel": "k_range_scan+k_gather",
+        "scan_only_GBps": round((p["rows_scanned"] * 16) / (p["scan_ms"] / 1e3) / 1e9, 2)
+                          if p["scan_ms"] > 0 else None,
+        "note": "achieved = (rows_scanned x 16B + gathered bytes) / HIP-event "
+                "kernel time on the store stream",
+    }
+
+    # PMC-measured HBM traffic per launch (profiles/pmc_traffic.json,
+    # collected with rocprofv3 --pmc FETCH_SIZE on this same workload)
+    try:
+        tj = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
+        per_launch = (tj["scan_bytes_per_launch"] * tj.get("scan_correction", 1)
+                      + tj["gather_bytes_per_launch"])
+        roofline["traffic"] = int(per_launch)
+        roofline["traffic_note"] = tj["_source"]
+    except Exception:
+        pass
+
+    # the result line of a plain run: the headline figure and what the timed
+    # steps' own counters give for free (--full adds the other legs' keys)
+    result = {
+        "metric": "range+txn ops/s (90/10, Range limit=500) + watch events/s",
+        "value": round(value, 1),
+        "unit": "ops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": f"10M-key MVCC slab headline config: "
+                        f"{args.nns * args.per_ns // 1000000}M Pod-style keys / "
+                        f"{args.extra_revs} extra revisions (zipf 1.1) / 2% "
+                        f"tombstones, Range(limit=500)+Txn conditional-update "
+                        f"90/10, 512B values, single MI355X"
+                        if world == 1 else
+                        f"10M-key headline config sharded by namespace hash "
+                        f"over {world} GPUs (weak scaling)",
+            "n_keys": args.nns * args.per_ns,
+            "extra_revs": args.extra_revs,
+            "limit": LIMIT,
+            "ops_per_step": OPS_PER_STEP,
+            "watchers": max(args.watchers // world, 8) * world,
+        },
+        "step_split_ms": {"range": round(split_snapshot["range_s"] / args.steps * 1e3, 3),
+                          "txn": round(split_snapshot["txn_s"] / args.steps * 1e3, 3)},
+        "roofline": roofline,
+        "perf": p,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full only from here: every leg below takes runs of its own ----
+
+    # one-off PCIe reference: pinned D2H bandwidth of the host (torch copy)
+    # host-health probe: host spin speed + GPU sclk, reported with the line
+    # (host-to-host variance reaches 3x; a slow `value` with a slow probe is
+    # the machine, not the code)
     box = {}
     try:
         t0 = time.time()
@@ -744,8 +955,8 @@ def main():
         log(rank, f"[bench] compact sweep: {compact_stats}")
 
     # watch fan-out leg
-    wrate, delivered, watch_stats = watch_leg(store, my_ns_list, live, revs,
-                                              qrng,
+    wrate, delivered, watch_stats = watch_leg(store, my_ns_list, sel, live,
+                                              revs, qrng,
                                               max(args.watchers // world, 8),
                                               args.watch_events // world)
     if dist:
@@ -754,74 +965,13 @@ def main():
         dist.all_reduce(w, op=dist.ReduceOp.SUM)
         wrate = float(w.item())
 
-    total_ops = OPS_PER_STEP * args.steps * world
-    value = total_ops / elapsed
-    # roofline over the range path (scan + winner gather), per SURVEY §8d's
-    # algorithmic bytes: 16B per row scanned (meta+rev, DESIGN.md §3.3) +
-    # gathered record bytes (key+value+header per winner)
-    rng_s = (p["scan_ms"] + p["gather_ms"]) / 1e3
-    alg_bytes = p["rows_scanned"] * 16 + p["bytes_gathered"]
-    achieved = alg_bytes / rng_s if rng_s > 0 else 0.0
-    peak = 8.0e12
-    roofline = {
-        "bound": "hbm",
-        "achieved": round(achieved / 1e9, 2),
-        "peak": peak / 1e9,
-        "unit": "GB/s",
-        "frac": round(achieved / peak, 4),
-        "traffic": None,  # filled below from the committed PMC sidecar
-        "kernel": "k_range_scan+k_gather",
-        "scan_only_GBps": round((p["rows_scanned"] * 16) / (p["scan_ms"] / 1e3) / 1e9, 2)
-                          if p["scan_ms"] > 0 else None,
-        "note": "achieved = (rows_scanned x 16B + gathered bytes) / HIP-event "
-                "kernel time on the store stream",
-    }
-
-    # PMC-measured HBM traffic per launch (profiles/pmc_traffic.json,
-    # collected with rocprofv3 --pmc FETCH_SIZE on this same workload)
-    try:
-        tj = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
-        per_launch = (tj["scan_bytes_per_launch"] * tj.get("scan_correction", 1)
-                      + tj["gather_bytes_per_launch"])
-        roofline["traffic"] = int(per_launch)
-        roofline["traffic_note"] = tj["_source"]
-    except Exception:
-        pass
-
     cpu_baseline = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         log(rank, "[bench] cpu baseline (oracle, bounded sample)...")
         cpu_baseline = cpu_baseline_leg(namespaces, keys, [])
 
     if rank == 0:
-        out = {
-            "metric": "range+txn ops/s (90/10, Range limit=500) + watch events/s",
-            "value": round(value, 1),
-            "unit": "ops/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": f"10M-key MVCC slab headline config: "
-                            f"{args.nns * args.per_ns // 1000000}M Pod-style keys / "
-                            f"{args.extra_revs} extra revisions (zipf 1.1) / 2% "
-                            f"tombstones, Range(limit=500)+Txn conditional-update "
-                            f"90/10, 512B values, single MI355X"
-                            if world == 1 else
-                            f"10M-key headline config sharded by namespace hash "
-                            f"over {world} GPUs (weak scaling)",
-                "n_keys": args.nns * args.per_ns,
-                "extra_revs": args.extra_revs,
-                "limit": LIMIT,
-                "ops_per_step": OPS_PER_STEP,
-                "watchers": max(args.watchers // world, 8) * world,
-            },
+        result.update({
             "cross_shard_range": cross_shard,
             "compact_sweep": compact_stats,
             "watch_events_per_sec": round(wrate, 1),
@@ -834,18 +984,14 @@ def main():
             "d2h_keys_only_detail": d2h_ko_detail,
             "pcie_d2h_GBps": pcie_gbps,
             "box": box,
-            "step_split_ms": {"range": round(split_snapshot["range_s"] / args.steps * 1e3, 3),
-                               "txn": round(split_snapshot["txn_s"] / args.steps * 1e3, 3)},
-            "roofline": roofline,
             "cpu_baseline": cpu_baseline,
             # one-off FULL-keyspace CPU measurement (tests/cpu_full_baseline.py
-            # on the GPU box's 256 cores; committed artifact — the in-run
-            # bounded sample above overstates the CPU, its subset being
+            # on a 256-core host; committed artifact — the in-run bounded
+            # sample above overstates the CPU, its subset being
             # cache-friendlier)
             "cpu_baseline_full_config": _load_full_cpu_baseline(),
-            "perf": p,
-        }
-        print(json.dumps(out))
+        })
+        print(json.dumps(result))
     if dist:
         dist.destroy_process_group()
 

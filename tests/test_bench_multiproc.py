@@ -115,9 +115,9 @@ def _worker(rank, world, port, outdir):
     kubebrain_amd.open_store = lambda **kw: MockStore(**kw)
     import bench
 
-    sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--nns", "16",
-                "--per-ns", "10", "--extra-revs", "50", "--watchers", "4",
-                "--watch-events", "30", "--no-cpu-baseline"]
+    sys.argv = ["bench.py", "--full", "--steps", "3", "--warmup", "1",
+                "--nns", "16", "--per-ns", "10", "--extra-revs", "50",
+                "--watchers", "4", "--watch-events", "30", "--no-cpu-baseline"]
     import io
     import contextlib
     cap = io.StringIO()
