@@ -99,6 +99,26 @@ long long kb_watch(kb_store*, const uint8_t* prefix, size_t plen, uint64_t rev,
  * queue is left INTACT (*out_len = required size): retry with a larger
  * buffer and no event is lost. */
 int kb_watch_poll(kb_store*, long long wid, uint8_t* out, size_t cap, size_t* out_len);
+/* Poll n watchers in one call (watch.go:119-159 per watcher; watcherhub.go:78-100).
+ * out = u32 n; then n x { i32 status; u32 len; len bytes }, in the order of wids[].
+ * For status KB_OK the len bytes are EXACTLY what kb_watch_poll(wid) would have
+ * written (u32 count; count x event). For any other status len = 0.
+ * KB_ENOBUF: *out_len = required size of the whole reply, NO queue is drained,
+ * and the call can be repeated with a larger buffer with the same result.
+ * Nothing is written when cap < 4.
+ * Per-watcher status is what kb_watch_poll returns: an unknown, cancelled or
+ * slow-consumer wid gives KB_EWATCH_DROPPED (and is erased once the call
+ * succeeds). A duplicate wid in wids[] returns KB_EINVALID and changes
+ * nothing. n == 0 is valid (out = u32 0). *total_events = sum of the
+ * per-watcher counts. May be interleaved freely with kb_watch_poll.
+ * The first call arms a device payload ring (KB_WATCH_PAYLOAD_BYTES, default
+ * 256 MiB, 0 = off): from then on each event is serialized once into HBM and
+ * sections are assembled by HIP kernels; watchers whose
+ * events are not resident there are served by the host serializer with
+ * identical bytes. */
+int kb_watch_poll_batch(kb_store*, const long long* wids, size_t n,
+                        uint8_t* out, size_t cap, size_t* out_len,
+                        unsigned long long* total_events);
 void kb_watch_cancel(kb_store*, long long wid);
 
 /* ---- streaming full-range reads (backend.ListByStream range.go:247-256 +
@@ -146,6 +166,22 @@ int kb_range_global(kb_store*, const uint8_t* start, size_t slen,
 int kb_test_merge_runs(const uint8_t* runs_cat, const unsigned long long* lens,
                        int world, long long limit, uint8_t* out, size_t cap,
                        size_t* out_len, int* more);
+/* TEST-ONLY: the pure host reply planner of kb_watch_poll_batch (no GPU, no
+ * store). Inputs: nrefs device refs in watcher order as parallel arrays
+ * {bytes, count, watcher_index}; per watcher its status and host_len (size of
+ * a host-serialized section, >= 4; < 0 = device path, section = 4 + its refs'
+ * bytes); cap. Outputs (caller arrays, may be NULL): per watcher the
+ * directory len, the device event count and the offset of its section
+ * bytes; per ref the offset of its first record; *required = reply size.
+ * Returns KB_OK, KB_ENOBUF (required > cap) or KB_EINVALID (refs out of
+ * order or naming a watcher that is not on the device path). */
+int kb_test_wpoll_plan(const unsigned long long* ref_bytes,
+                       const unsigned int* ref_count, const int* ref_widx,
+                       size_t nrefs, const int* status,
+                       const long long* host_len, size_t n, size_t cap,
+                       unsigned int* dir_len, unsigned int* dir_count,
+                       unsigned long long* sec_off,
+                       unsigned long long* ref_off, size_t* required);
 
 /* ---- revision (tso/tso.go:41-76) ---- */
 unsigned long long kb_current_rev(kb_store*);

@@ -362,6 +362,63 @@ func (b *amdBackend) Watch(ctx context.Context, key string, revision uint64) (<-
 	return ch, nil
 }
 
+// WatchSection is one watcher's share of a batched poll: Status is what
+// kb_watch_poll would have returned for that watcher (KB_EWATCH_DROPPED for an
+// unknown, cancelled or slow-consumer wid) and Events its decoded section.
+type WatchSection struct {
+	Status int
+	Events []*proto.Event
+}
+
+// WatchPollBatch polls many watchers (the wids kb_watch returned) with ONE
+// kb_watch_poll_batch call: the sections are serialized on the GPU from the
+// device payload ring instead of one host walk per watcher. A hub that owns
+// all watch channels calls this from a single poller goroutine in place of
+// the per-watcher goroutines of Watch above. Same ENOBUF grow-and-retry
+// contract as every other call: a too-small buffer drains nothing.
+// Not part of the Backend interface, and like the rest of this file it has
+// not been seen by a Go compiler (see the NOTE at the top); the executable
+// specification of the reply format is kubebrain_amd/client.py
+// watch_poll_batch + tests/test_gpu_watch_poll_batch.py.
+func (b *amdBackend) WatchPollBatch(wids []int64, buf []byte) ([]WatchSection, []byte, error) {
+	if len(buf) < 4 {
+		buf = make([]byte, 4<<20)
+	}
+	cw := make([]C.longlong, len(wids)+1)
+	for i, w := range wids {
+		cw[i] = C.longlong(w)
+	}
+	for {
+		var outLen C.size_t
+		var total C.ulonglong
+		rc := C.kb_watch_poll_batch(b.h, &cw[0], C.size_t(len(wids)),
+			bptr(buf), C.size_t(len(buf)), &outLen, &total)
+		if rc == C.KB_ENOBUF { // nothing drained; out_len carries need
+			buf = make([]byte, int(outLen))
+			continue
+		}
+		if rc != C.KB_OK {
+			return nil, buf, statusToErr(rc)
+		}
+		// reply = u32 n; n x { i32 status; u32 len; len bytes }
+		n := int(binary.LittleEndian.Uint32(buf))
+		off := 4
+		out := make([]WatchSection, 0, n)
+		for i := 0; i < n; i++ {
+			st := int(int32(binary.LittleEndian.Uint32(buf[off:])))
+			ln := int(binary.LittleEndian.Uint32(buf[off+4:]))
+			off += 8
+			sec := WatchSection{Status: st}
+			if st == int(C.KB_OK) {
+				sec.Events = decodeEvents(buf[off : off+ln])
+			}
+			off += ln
+			out = append(out, sec)
+		}
+		return out, buf, nil
+	}
+}
+
 // decodeEvents parses kb_watch_poll's wire format {u32 n; n x {i32 type;
 // u64 rev; u64 kv_rev; u32 klen; key; u32 vlen; val}}
 // (executable spec: tests/kbclient.py _parse_events).

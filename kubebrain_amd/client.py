@@ -192,6 +192,41 @@ class Store:
             return rc, []
         return rc, _parse_events(self.buf[:out_len.value])
 
+    def watch_poll_batch(self, wids):
+        """Poll many watchers in one call (kb_watch_poll_batch; product ABI
+        only). Returns (rc, [(status, [Ev...]), ...], raw_sections) in the
+        order of wids; raw_sections[i] holds the section's bytes exactly as
+        kb_watch_poll would have written them (b"" for a non-OK status).
+        KB_ENOBUF is handled here by growing the buffer and repeating the
+        call (nothing is drained by the failed attempt)."""
+        n = len(wids)
+        arr = (C.c_longlong * max(n, 1))(*wids)
+        out_len = C.c_size_t(); total = C.c_ulonglong()
+        f = self._f("watch_poll_batch")
+        buf, cap = self.buf, self.BUF
+        for _ in range(4):
+            rc = f(C.c_void_p(self.h), arr, C.c_size_t(n), buf, C.c_size_t(cap),
+                   C.byref(out_len), C.byref(total))
+            if rc != ENOBUF:
+                break
+            cap = out_len.value
+            buf = C.create_string_buffer(cap)
+        if rc != OK:
+            return rc, [], []
+        raw = C.string_at(buf, out_len.value)
+        (cnt,) = struct.unpack_from("<I", raw, 0)
+        assert cnt == n, (cnt, n)
+        off = 4
+        res, sections = [], []
+        for _ in range(n):
+            st, ln = struct.unpack_from("<iI", raw, off); off += 8
+            sec = raw[off:off + ln]; off += ln
+            sections.append(sec)
+            res.append((st, _parse_events(sec) if st == OK else []))
+        assert off == len(raw), (off, len(raw))
+        assert sum(len(e) for _, e in res) == total.value
+        return rc, res, sections
+
     def watch_cancel(self, wid: int):
         self._f("watch_cancel")(C.c_void_p(self.h), C.c_longlong(wid))
 

@@ -206,6 +206,47 @@ int kb_watch_poll(kb_store* h, long long wid, uint8_t* out, size_t cap,
   return st;
 }
 
+int kb_watch_poll_batch(kb_store* h, const long long* wids, size_t n,
+                        uint8_t* out, size_t cap, size_t* out_len,
+                        unsigned long long* total_events) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "wid width");
+  std::string err;
+  size_t len = 0;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->WatchPollBatch((const int64_t*)wids, n, out, cap,
+                                          &len, &total, &err);
+  if (out_len) *out_len = len;
+  if (total_events) *total_events = total;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
+int kb_test_wpoll_plan(const unsigned long long* ref_bytes,
+                       const unsigned int* ref_count, const int* ref_widx,
+                       size_t nrefs, const int* status,
+                       const long long* host_len, size_t n, size_t cap,
+                       unsigned int* dir_len, unsigned int* dir_count,
+                       unsigned long long* sec_off,
+                       unsigned long long* ref_off, size_t* required) {
+  std::vector<kbwpoll::PlanRef> refs(nrefs);
+  for (size_t i = 0; i < nrefs; ++i)
+    refs[i] = kbwpoll::PlanRef{ref_bytes[i], ref_count[i], ref_widx[i]};
+  std::vector<int32_t> st(status, status + n);
+  std::vector<int64_t> hl(host_len, host_len + n);
+  kbwpoll::PlanOut o;
+  int rc = kbwpoll::Plan(refs.data(), nrefs, st.data(), hl.data(), n, cap, &o);
+  if (rc != KB_OK && rc != KB_ENOBUF) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (dir_len) dir_len[i] = o.len[i];
+    if (dir_count) dir_count[i] = o.count[i];
+    if (sec_off) sec_off[i] = o.sec_off[i];
+  }
+  for (size_t i = 0; i < nrefs && ref_off; ++i) ref_off[i] = o.ref_off[i];
+  if (required) *required = (size_t)o.required;
+  return rc;
+}
+
 void kb_watch_cancel(kb_store* h, long long wid) { ((Store*)h)->WatchCancel(wid); }
 
 long long kb_stream_open(kb_store* h, const uint8_t* start, size_t slen,

@@ -1186,6 +1186,153 @@ __global__ void k_watch_catchup(const uint8_t* __restrict__ er_keys,
   if (lane == 0 && e < count) words[e >> 6] = b;
 }
 
+// ---- batched watch poll: serialize deliveries on the device --------------
+// (kb_watch_poll_batch). Next to (key96, rev) the event ring
+// carries er_poff/er_plen: where each event's wire record (i32 type | u64
+// rev | u64 kv_rev | u32 klen | key | u32 vlen | val, serialized ONCE by the
+// host at pump time) sits in the payload byte ring. A delivery is then a
+// byte copy: one wave per bitmap ref, 4 waves per block.
+
+__device__ __forceinline__ uint64_t wp_shfl64(uint64_t v, int src) {
+  uint32_t lo = __shfl((uint32_t)v, src, 64);
+  uint32_t hi = __shfl((uint32_t)(v >> 32), src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// inclusive wave prefix sum (64 lanes)
+__device__ __forceinline__ uint64_t wp_scan64(uint64_t v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    uint32_t lo = __shfl_up((uint32_t)v, d, 64);
+    uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
+    if (lane >= d) v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+
+// lane l takes bit l of each word; a wave reduction yields {bytes, count}
+__global__ __launch_bounds__(256) void k_wpoll_size(
+    const WpollRef* __restrict__ refs, int64_t nrefs,
+    const uint32_t* __restrict__ er_plen, int64_t ring_cap,
+    WpollSize* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= nrefs) return;  // wave-uniform
+  const WpollRef* ref = refs + r;
+  const int64_t base = ref->base;
+  const int32_t count = ref->count;
+  uint64_t bytes = 0;
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    if (c * 64 + lane < count && ((ref->words[c] >> lane) & 1)) {
+      bytes += er_plen[(base + c * 64 + lane) % ring_cap];
+      ++cnt;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    uint32_t lo = __shfl_xor((uint32_t)bytes, d, 64);
+    uint32_t hi = __shfl_xor((uint32_t)(bytes >> 32), d, 64);
+    bytes += ((uint64_t)hi << 32) | lo;
+    cnt += __shfl_xor(cnt, d, 64);
+  }
+  if (lane == 0) {
+    WpollSize s;
+    s.bytes = bytes;
+    s.count = cnt;
+    s._pad = 0;
+    out[r] = s;
+  }
+}
+
+// wave-cooperative copy of one record: src is 16-byte aligned (payload ring
+// placement), dst is arbitrarily aligned (the wire format is packed). The
+// body goes out as ALIGNED 16-byte destination stores, each built from two
+// aligned 16-byte source loads by a funnel shift; the up-to-15 head bytes
+// before the first aligned destination address and the up-to-15 tail bytes
+// go out as single byte stores. Neighbouring records are written by other
+// waves and may share a destination dword/qword with this one, so no wide
+// store ever reaches outside [dst, dst+len).
+__device__ __forceinline__ void wp_copy_record(const uint8_t* __restrict__ src,
+                                               uint8_t* __restrict__ dst,
+                                               uint32_t len, int lane) {
+  uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+  if (head > len) head = len;
+  if ((uint32_t)lane < head) dst[lane] = src[lane];
+  const uint32_t nq = (len - head) >> 4;      // full aligned 16 B stores
+  const uint32_t shb = head & 15;             // src misalignment of the body
+  const uint32_t wsh = shb >> 2, bsh = (shb & 3) * 8;
+  const uint4* s4 = (const uint4*)(src + (head & ~15u));  // == src
+  uint4* d4 = (uint4*)(dst + head);
+  for (uint32_t i = lane; i < nq; i += 64) {
+    uint4 a = s4[i];
+    // the second source quad is needed (and guaranteed inside the record's
+    // 16 B-aligned extent) only when the body is misaligned
+    uint4 b = shb ? s4[i + 1] : make_uint4(0, 0, 0, 0);
+    uint32_t t0, t1, t2, t3, t4;
+    switch (wsh) {  // wave-uniform: no indexed register array, no scratch
+      case 0: t0 = a.x; t1 = a.y; t2 = a.z; t3 = a.w; t4 = b.x; break;
+      case 1: t0 = a.y; t1 = a.z; t2 = a.w; t3 = b.x; t4 = b.y; break;
+      case 2: t0 = a.z; t1 = a.w; t2 = b.x; t3 = b.y; t4 = b.z; break;
+      default: t0 = a.w; t1 = b.x; t2 = b.y; t3 = b.z; t4 = b.w; break;
+    }
+    uint4 o;
+    o.x = (uint32_t)((((uint64_t)t1 << 32) | t0) >> bsh);
+    o.y = (uint32_t)((((uint64_t)t2 << 32) | t1) >> bsh);
+    o.z = (uint32_t)((((uint64_t)t3 << 32) | t2) >> bsh);
+    o.w = (uint32_t)((((uint64_t)t4 << 32) | t3) >> bsh);
+    d4[i] = o;
+  }
+  const uint32_t done = head + (nq << 4);
+  if ((uint32_t)lane < len - done) dst[done + lane] = src[done + lane];
+}
+
+// one wave per ref: recompute per-event offsets with a wave prefix sum in
+// (word, lane) order == ascending revision == WatchPollWire's order, then
+// copy each record, the whole wave cooperating on one record at a time
+__global__ __launch_bounds__(256) void k_wpoll_emit(
+    const WpollRef* __restrict__ refs, const uint64_t* __restrict__ ref_off,
+    int64_t nrefs, const uint64_t* __restrict__ er_poff,
+    const uint32_t* __restrict__ er_plen, int64_t ring_cap,
+    const uint8_t* __restrict__ pay, int64_t pay_cap,
+    uint8_t* __restrict__ arena, int64_t arena_cap) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= nrefs) return;  // wave-uniform
+  const WpollRef* ref = refs + r;
+  const int64_t base = ref->base;
+  const int32_t count = ref->count;
+  uint64_t run = ref_off[r];  // destination of the next word's first record
+  for (int c = 0; c < 8 && c * 64 < count; ++c) {
+    const bool bit = c * 64 + lane < count && ((ref->words[c] >> lane) & 1);
+    uint64_t poff = 0;
+    uint32_t plen = 0;
+    if (bit) {
+      int64_t slot = (base + c * 64 + lane) % ring_cap;
+      poff = er_poff[slot];
+      plen = er_plen[slot];
+    }
+    const uint64_t incl = wp_scan64(plen, lane);
+    const uint64_t doff = run + incl - plen;
+    uint64_t mask = __ballot(bit);
+    while (mask) {  // wave-uniform
+      const int j = __builtin_ctzll(mask);
+      mask &= mask - 1;
+      const uint64_t so = wp_shfl64(poff, j);
+      const uint64_t dd = wp_shfl64(doff, j);
+      const uint32_t ln = __shfl(plen, j, 64);
+      // defensive bounds: a record the host did not place inside the ring
+      // or the arena is skipped, never copied out of bounds
+      if (so + (((uint64_t)ln + 15) & ~15ull) > (uint64_t)pay_cap ||
+          dd + ln > (uint64_t)arena_cap)
+        continue;
+      wp_copy_record(pay + so, arena + dd, ln, lane);
+    }
+    run += wp_shfl64(incl, 63);
+  }
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -1323,6 +1470,51 @@ struct Slab::Impl {
   uint64_t* d_bitmap = nullptr;
   int64_t bitmap_cap = 0;
 
+  // payload ring + batched poll (all allocated lazily: PayloadArm / first
+  // use). er_poff/er_plen are event-ring columns; pay is the byte ring.
+  uint64_t* er_poff = nullptr;
+  uint32_t* er_plen = nullptr;
+  uint8_t* pay = nullptr;
+  int64_t pay_cap = 0;
+  uint8_t* h_pstage = nullptr;   // pinned payload staging
+  int64_t h_pstage_cap = 0;
+  hipEvent_t ev_w0 = nullptr, ev_w1 = nullptr, ev_w2 = nullptr;
+  WpollRef *h_wrefs = nullptr, *d_wrefs = nullptr;   // ref table
+  WpollSize *h_wsizes = nullptr, *d_wsizes = nullptr;
+  uint64_t *h_woffs = nullptr, *d_woffs = nullptr;
+  int64_t wrefs_cap = 0;
+  uint8_t *d_warena = nullptr, *h_wreply = nullptr;
+  int64_t warena_cap = 0, wreply_cap = 0;
+  void free_wpoll() {
+    for (void* q : {(void*)er_poff, (void*)er_plen, (void*)pay, (void*)d_wrefs,
+                    (void*)d_wsizes, (void*)d_woffs, (void*)d_warena})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_pstage, (void*)h_wrefs, (void*)h_wsizes,
+                    (void*)h_woffs, (void*)h_wreply})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_w0, ev_w1, ev_w2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_wrefs(int64_t nrefs, std::string* err) {
+    if (nrefs <= wrefs_cap) return true;
+    int64_t cap = std::max<int64_t>(1024, nrefs + nrefs / 2);
+    for (void* q : {(void*)d_wrefs, (void*)d_wsizes, (void*)d_woffs})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_wrefs, (void*)h_wsizes, (void*)h_woffs})
+      if (q) (void)hipHostFree(q);
+    d_wrefs = nullptr; d_wsizes = nullptr; d_woffs = nullptr;
+    h_wrefs = nullptr; h_wsizes = nullptr; h_woffs = nullptr;
+    wrefs_cap = 0;
+    HIP_CHECK(hipMalloc(&d_wrefs, cap * sizeof(WpollRef)));
+    HIP_CHECK(hipMalloc(&d_wsizes, cap * sizeof(WpollSize)));
+    HIP_CHECK(hipMalloc(&d_woffs, cap * 8));
+    HIP_CHECK(hipHostMalloc(&h_wrefs, cap * sizeof(WpollRef)));
+    HIP_CHECK(hipHostMalloc(&h_wsizes, cap * sizeof(WpollSize)));
+    HIP_CHECK(hipHostMalloc(&h_woffs, cap * 8));
+    wrefs_cap = cap;
+    return true;
+  }
+
   // KB_SCAN_DBG=1: per-phase wall_clock64 cycle sums from k_range_scan2
   // ([0]=bounds [1]=pass1a [2]=pass1b [3]=scatter [4]=merge [5]=block total)
   unsigned long long* d_dbg = nullptr;
@@ -1419,6 +1611,7 @@ struct Slab::Impl {
                     (void*)er_keys, (void*)er_rev, (void*)d_bitmap}) {
       if (p) (void)hipFree(p);
     }
+    free_wpoll();
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_resmeta) (void)hipHostFree(h_resmeta);
     for (int i = 0; i < 2; ++i) {
@@ -2591,6 +2784,163 @@ bool Slab::WatchCatchup(const uint8_t* pfx96, uint32_t plen, uint64_t from_rev,
   perf.filter_launches++;
   perf.filter_events += count;
   perf.filter_watchers += 1;
+  return true;
+}
+
+// ---- payload ring + batched poll ------------------------------------------
+
+bool Slab::PayloadArm(int64_t ring_bytes, std::string* err) {
+  Impl* I = p;
+  if (I->pay) return true;
+  if (!I->er_keys) { if (err) *err = "event ring not initialized"; return false; }
+  if (ring_bytes < 16) { if (err) *err = "payload ring too small"; return false; }
+  HIP_CHECK(hipMalloc(&I->er_poff, I->er_cap * 8));
+  HIP_CHECK(hipMalloc(&I->er_plen, I->er_cap * 4));
+  HIP_CHECK(hipMemsetAsync(I->er_poff, 0, I->er_cap * 8, I->stream));
+  HIP_CHECK(hipMemsetAsync(I->er_plen, 0, I->er_cap * 4, I->stream));
+  HIP_CHECK(hipEventCreate(&I->ev_w0));
+  HIP_CHECK(hipEventCreate(&I->ev_w1));
+  HIP_CHECK(hipEventCreate(&I->ev_w2));
+  HIP_CHECK(hipMalloc(&I->pay, ring_bytes));
+  I->pay_cap = ring_bytes;
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  return true;
+}
+
+uint8_t* Slab::PayloadStaging(int64_t need, std::string* err) {
+  Impl* I = p;
+  if (need > I->h_pstage_cap) {
+    if (I->h_pstage) (void)hipHostFree(I->h_pstage);
+    I->h_pstage = nullptr;
+    I->h_pstage_cap = 0;
+    int64_t cap = std::max<int64_t>(1 << 20, need + need / 2);
+    HIP_CHECK_NULL(hipHostMalloc(&I->h_pstage, cap));
+    I->h_pstage_cap = cap;
+  }
+  return I->h_pstage;
+}
+
+bool Slab::PayloadPush(const PaySeg* segs, size_t nsegs, const uint64_t* poffs,
+                       const uint32_t* plens, int64_t count, int64_t base_seq,
+                       std::string* err) {
+  Impl* I = p;
+  if (!I->pay) { if (err) *err = "payload ring not armed"; return false; }
+  for (size_t i = 0; i < nsegs; ++i) {
+    const PaySeg& s = segs[i];
+    if (s.len <= 0) continue;
+    if (s.ring_off < 0 || s.ring_off + s.len > I->pay_cap || s.stage_off < 0 ||
+        s.stage_off + s.len > I->h_pstage_cap) {
+      if (err) *err = "payload segment out of bounds";
+      return false;
+    }
+    HIP_CHECK(hipMemcpyAsync(I->pay + s.ring_off, I->h_pstage + s.stage_off,
+                             s.len, hipMemcpyHostToDevice, I->stream));
+  }
+  // column entries; contiguous seqs, the ring may wrap once per push
+  int64_t s0 = base_seq % I->er_cap;
+  int64_t first = std::min(count, I->er_cap - s0);
+  HIP_CHECK(hipMemcpyAsync(I->er_poff + s0, poffs, first * 8,
+                           hipMemcpyHostToDevice, I->stream));
+  HIP_CHECK(hipMemcpyAsync(I->er_plen + s0, plens, first * 4,
+                           hipMemcpyHostToDevice, I->stream));
+  if (first < count) {
+    HIP_CHECK(hipMemcpyAsync(I->er_poff, poffs + first, (count - first) * 8,
+                             hipMemcpyHostToDevice, I->stream));
+    HIP_CHECK(hipMemcpyAsync(I->er_plen, plens + first, (count - first) * 4,
+                             hipMemcpyHostToDevice, I->stream));
+  }
+  // the staging buffer and the caller's vectors are reused by the next push
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  return true;
+}
+
+WpollRef* Slab::WpollRefStaging(int64_t nrefs, std::string* err) {
+  if (!p->ensure_wrefs(nrefs, err)) return nullptr;
+  return p->h_wrefs;
+}
+
+uint64_t* Slab::WpollOffStaging(int64_t nrefs, std::string* err) {
+  if (!p->ensure_wrefs(nrefs, err)) return nullptr;
+  return p->h_woffs;
+}
+
+bool Slab::WpollSizeRefs(int64_t nrefs, const WpollSize** sizes,
+                         std::string* err) {
+  Impl* I = p;
+  if (!I->pay || nrefs <= 0 || nrefs > I->wrefs_cap) {
+    if (err) *err = "wpoll: not armed or bad ref count";
+    return false;
+  }
+  HIP_CHECK(hipMemcpyAsync(I->d_wrefs, I->h_wrefs, nrefs * sizeof(WpollRef),
+                           hipMemcpyHostToDevice, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_w0, I->stream));
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launch
+  hipLaunchKernelGGL(k_wpoll_size, dim3((uint32_t)ceil_div(nrefs, 4)),
+                     dim3(256), 0, I->stream, I->d_wrefs, nrefs, I->er_plen,
+                     I->er_cap, I->d_wsizes);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_w1, I->stream));
+  HIP_CHECK(hipMemcpyAsync(I->h_wsizes, I->d_wsizes, nrefs * sizeof(WpollSize),
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_w0, I->ev_w1);
+  perf.wpoll_ms += ms;
+  perf.wpoll_launches++;
+  *sizes = I->h_wsizes;
+  return true;
+}
+
+bool Slab::WpollEmit(int64_t nrefs, int64_t lo, int64_t hi, int64_t total,
+                     uint8_t** reply, std::string* err) {
+  Impl* I = p;
+  if (!I->pay || nrefs <= 0 || nrefs > I->wrefs_cap || lo < 0 || hi < lo ||
+      hi > total) {
+    if (err) *err = "wpoll: not armed or bad emit span";
+    return false;
+  }
+  if (total > I->warena_cap) {
+    if (I->d_warena) (void)hipFree(I->d_warena);
+    I->d_warena = nullptr;
+    I->warena_cap = 0;
+    int64_t cap = std::max<int64_t>(1 << 20, total + total / 2);
+    // +16: the copy's aligned 16 B loads never leave a record's padded
+    // extent, the slack keeps the arena's last store inside the allocation
+    HIP_CHECK(hipMalloc(&I->d_warena, cap + 16));
+    I->warena_cap = cap;
+  }
+  if (total > I->wreply_cap) {
+    if (I->h_wreply) (void)hipHostFree(I->h_wreply);
+    I->h_wreply = nullptr;
+    I->wreply_cap = 0;
+    int64_t cap = std::max<int64_t>(1 << 20, total + total / 2);
+    HIP_CHECK(hipHostMalloc(&I->h_wreply, cap));
+    I->wreply_cap = cap;
+  }
+  HIP_CHECK(hipMemcpyAsync(I->d_woffs, I->h_woffs, nrefs * 8,
+                           hipMemcpyHostToDevice, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_w0, I->stream));
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_wpoll_emit, dim3((uint32_t)ceil_div(nrefs, 4)),
+                     dim3(256), 0, I->stream, I->d_wrefs, I->d_woffs, nrefs,
+                     I->er_poff, I->er_plen, I->er_cap, I->pay, I->pay_cap,
+                     I->d_warena, total);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_w1, I->stream));
+  if (hi > lo)
+    HIP_CHECK(hipMemcpyAsync(I->h_wreply + lo, I->d_warena + lo, hi - lo,
+                             hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_w2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_w0, I->ev_w1);
+  perf.wpoll_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_w1, I->ev_w2);
+  perf.wpoll_d2h_ms += ms;
+  perf.wpoll_launches++;
+  perf.wpoll_bytes += hi - lo;
+  *reply = I->h_wreply;
   return true;
 }
 

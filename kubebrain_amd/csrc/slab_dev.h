@@ -115,7 +115,31 @@ struct Perf {
   int64_t rows_scanned = 0, bytes_gathered = 0, winners = 0,
           filter_events = 0, filter_watchers = 0;
   double dbg_a = 0, dbg_b = 0, dbg_c = 0, dbg_d = 0, dbg_e = 0;
+  // batched watch poll (kb_watch_poll_batch): k_wpoll_size + k_wpoll_emit
+  // kernel time, the reply D2H, events served per path, device bytes moved
+  double wpoll_ms = 0, wpoll_d2h_ms = 0;
+  int64_t wpoll_launches = 0, wpoll_events_dev = 0, wpoll_events_host = 0,
+          wpoll_bytes = 0;
 };
+
+// batched watch poll: one delivery bitmap reference (<= 512 events of the
+// event ring starting at sequence `base`) of the watcher at index widx of
+// the call's wids[]
+struct WpollRef {
+  int64_t base;
+  int32_t count;
+  int32_t widx;
+  uint64_t words[8];
+};
+static_assert(sizeof(WpollRef) == 80, "ref table entry layout");
+// k_wpoll_size result per ref
+struct WpollSize {
+  uint64_t bytes;
+  uint32_t count;
+  uint32_t _pad;
+};
+// one contiguous piece of a payload push: staging bytes -> byte-ring offset
+struct PaySeg { int64_t ring_off, stage_off, len; };
 
 
 
@@ -224,6 +248,30 @@ class Slab {
   bool WatchCatchup(const uint8_t* pfx96, uint32_t plen, uint64_t from_rev,
                     int64_t base_seq, int64_t count,
                     std::vector<uint64_t>* words_out, std::string* err);
+  // device payload ring: per-event er_poff/er_plen columns
+  // next to (key96, rev) plus a byte ring holding each event in wire form.
+  // Allocated by PayloadArm (first kb_watch_poll_batch); placement is the
+  // host's (wpoll.h PayRing). PayloadStaging returns pinned memory the host
+  // serializes into; PayloadPush copies its segments to the ring and the
+  // column entries for [base_seq, base_seq+count) on the store's stream.
+  bool PayloadArm(int64_t ring_bytes, std::string* err);
+  uint8_t* PayloadStaging(int64_t need, std::string* err);
+  bool PayloadPush(const PaySeg* segs, size_t nsegs, const uint64_t* poffs,
+                   const uint32_t* plens, int64_t count, int64_t base_seq,
+                   std::string* err);
+  // batched poll: pinned ref table / per-ref destination offsets the host
+  // fills in place (grown on demand; contents are not preserved on growth)
+  WpollRef* WpollRefStaging(int64_t nrefs, std::string* err);
+  uint64_t* WpollOffStaging(int64_t nrefs, std::string* err);
+  // upload the ref table, run k_wpoll_size, read back 16 B per ref (the
+  // result points into pinned memory valid until the next call)
+  bool WpollSizeRefs(int64_t nrefs, const WpollSize** sizes, std::string* err);
+  // run k_wpoll_emit for the uploaded refs with the staged offsets: records
+  // land in a device arena laid out like the reply; bytes [lo, hi) then
+  // arrive in the pinned reply buffer (>= total bytes) with one D2H copy
+  bool WpollEmit(int64_t nrefs, int64_t lo, int64_t hi, int64_t total,
+                 uint8_t** reply, std::string* err);
+
   bool WatcherSet(int64_t slot, const uint8_t* prefix, uint32_t plen,
                   uint64_t from_rev, std::string* err);  // slot grows table
   void WatcherClear(int64_t slot);

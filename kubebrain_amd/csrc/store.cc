@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <thread>
 
 namespace kbstore {
 
@@ -97,6 +98,9 @@ Store* Store::Open(const Config& cfg_in, std::string* err) {
     }
   }
   s->keep_event_log_ = env_i64("KB_EVENT_LOG", 1) != 0;  // tests: on; bench: off
+  // byte ring of the batched poll; nothing is allocated until the first
+  // kb_watch_poll_batch call arms it (0 = host serializer only)
+  s->pay_cfg_bytes_ = env_i64("KB_WATCH_PAYLOAD_BYTES", s->pay_cfg_bytes_);
   return s;
 }
 
@@ -322,6 +326,11 @@ void Store::pumpEvents() {
     }
     if (!slab_->EventRingPush(ekeys.data(), erevs.data(), e, seq0 + (int64_t)b0,
                               &err)) {
+      fatal_ = err;
+      pending_.clear();
+      return;
+    }
+    if (pay_armed_ && !pushPayloads(b0, e, seq0 + (int64_t)b0, &err)) {
       fatal_ = err;
       pending_.clear();
       return;
@@ -683,6 +692,270 @@ Status Store::WatchPollWire(int64_t wid, uint8_t* out, size_t cap,
   *out_len = (size_t)(p - out);
   w.prefs.clear();
   w.pend_events = 0;
+  return OK;
+}
+
+// ---- batched poll (kb_watch_poll_batch) -------------------
+
+bool Store::armPayload(std::string* err) {
+  if (pay_armed_ || pay_cfg_bytes_ <= 0) return true;
+  int64_t bytes = pay_cfg_bytes_ & ~(int64_t)15;
+  if (bytes < 16) bytes = 16;
+  if (!slab_->PayloadArm(bytes, err)) return false;
+  // events before this point have no payload: the window starts here
+  pay_.init(bytes, ring_.l, ring_.e);
+  pay_armed_ = true;
+  return true;
+}
+
+// serialize pending_[b0, b0+count) once into pinned staging, laid out the
+// way the records land in the byte ring, and push them with their
+// er_poff/er_plen column entries
+bool Store::pushPayloads(size_t b0, int64_t count, int64_t base_seq,
+                         std::string* err) {
+  int64_t need = 0;
+  for (int64_t j = 0; j < count; ++j) {
+    const Event& ev = pending_[b0 + j];
+    uint64_t al = (kbwpoll::RecordSize(ev.kv_key.size(), ev.kv_value.size()) + 15) & ~15ull;
+    if (al <= (uint64_t)pay_.cap) need += (int64_t)al;
+  }
+  uint8_t* stage = need ? slab_->PayloadStaging(need, err) : nullptr;
+  if (need && !stage) return false;
+  std::vector<uint64_t> poffs((size_t)count, 0);
+  std::vector<uint32_t> plens((size_t)count, 0);
+  std::vector<kbslab::PaySeg> segs;
+  int64_t spos = 0;
+  for (int64_t j = 0; j < count; ++j) {
+    const Event& ev = pending_[b0 + j];
+    uint64_t len = kbwpoll::RecordSize(ev.kv_key.size(), ev.kv_value.size());
+    int64_t at = pay_.place(base_seq + j, len);
+    if (at < 0) continue;  // larger than the ring: host path serves it
+    int64_t al = (int64_t)((len + 15) & ~15ull);
+    uint8_t* end = kbwpoll::PutRecord(
+        stage + spos, (int32_t)ev.type, ev.revision, ev.kv_revision,
+        ev.kv_key.data(), (uint32_t)ev.kv_key.size(), ev.kv_value.data(),
+        (uint32_t)ev.kv_value.size());
+    memset(end, 0, (size_t)(al - (int64_t)len));
+    poffs[(size_t)j] = (uint64_t)at;
+    plens[(size_t)j] = (uint32_t)len;
+    if (!segs.empty() && segs.back().ring_off + segs.back().len == at &&
+        segs.back().stage_off + segs.back().len == spos)
+      segs.back().len += al;
+    else
+      segs.push_back(kbslab::PaySeg{at, spos, al});
+    spos += al;
+  }
+  return slab_->PayloadPush(segs.data(), segs.size(), poffs.data(),
+                            plens.data(), count, base_seq, err);
+}
+
+bool Store::refsStale(const Watcher& w) const {
+  for (const PendRef& pr : w.prefs)
+    if (pr.base < ring_.e - (int64_t)ring_.l) return true;
+  return false;
+}
+
+template <class W, class R, class Fn>
+static void eachPendingEvent(const W& w, const R& ring, Fn&& fn) {
+  const bool longpfx = w.prefix.size() > (size_t)KEYW;
+  for (const auto& pr : w.prefs)
+    for (int c = 0; c * 64 < pr.count; ++c) {
+      uint64_t bits = pr.words[c];
+      while (bits) {
+        int j = __builtin_ctzll(bits);
+        bits &= bits - 1;
+        const Event& ev = ring.arr[(pr.base + c * 64 + j) % ring.l];
+        // prefixes longer than the 96B device filter column: the bitmap is
+        // a superset; apply the exact prefix here
+        if (longpfx && ev.kv_key.compare(0, w.prefix.size(), w.prefix) != 0)
+          continue;
+        fn(ev);
+      }
+    }
+}
+
+size_t Store::wireSize(const Watcher& w, uint32_t* count) const {
+  size_t need = 4;
+  uint32_t cnt = 0;
+  eachPendingEvent(w, ring_, [&](const Event& ev) {
+    need += kbwpoll::RecordSize(ev.kv_key.size(), ev.kv_value.size());
+    ++cnt;
+  });
+  *count = cnt;
+  return need;
+}
+
+uint8_t* Store::wireEmit(const Watcher& w, uint8_t* p) const {
+  uint8_t* cntp = p;
+  p += 4;
+  uint32_t cnt = 0;
+  eachPendingEvent(w, ring_, [&](const Event& ev) {
+    p = kbwpoll::PutRecord(p, (int32_t)ev.type, ev.revision, ev.kv_revision,
+                           ev.kv_key.data(), (uint32_t)ev.kv_key.size(),
+                           ev.kv_value.data(), (uint32_t)ev.kv_value.size());
+    ++cnt;
+  });
+  memcpy(cntp, &cnt, 4);
+  return p;
+}
+
+// the one copy of the finished reply from the pinned buffer to the caller.
+// A large reply is split across a few threads: a single core copies at about
+// the rate the per-watcher host serializer already reaches, which would leave
+// the hand-over as the whole cost of the call.
+static void copyReply(uint8_t* dst, const uint8_t* src, size_t n) {
+  const size_t kPerThread = 4u << 20;
+  size_t nt = std::min<size_t>({n / kPerThread, (size_t)8,
+                                (size_t)std::thread::hardware_concurrency()});
+  if (nt <= 1) { memcpy(dst, src, n); return; }
+  const size_t chunk = ((n + nt - 1) / nt + 63) & ~(size_t)63;
+  std::vector<std::thread> th;
+  size_t off = chunk;  // this thread takes [0, chunk)
+  for (; off < n; off += chunk) {
+    size_t len = std::min(chunk, n - off);
+    try {
+      th.emplace_back([=] { memcpy(dst + off, src + off, len); });
+    } catch (...) {
+      break;  // no more threads: the rest is copied inline below
+    }
+  }
+  memcpy(dst, src, std::min(chunk, n));
+  if (off < n) memcpy(dst + off, src + off, n - off);
+  for (auto& t : th) t.join();
+}
+
+Status Store::WatchPollBatch(const int64_t* wids, size_t n, uint8_t* out,
+                             size_t cap, size_t* out_len,
+                             uint64_t* total_events, std::string* errp) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  pumpEvents();
+  *out_len = 0;
+  if (total_events) *total_events = 0;
+  if (n > 0x7fffffffull) return INVALID_ARG;
+  {
+    std::unordered_set<int64_t> seen;
+    for (size_t i = 0; i < n; ++i)
+      if (!seen.insert(wids[i]).second) return INVALID_ARG;
+  }
+  std::string errl;
+  std::string& err = errp ? *errp : errl;
+  if (!armPayload(&err)) return INTERNAL;
+
+  // pass 1: per-watcher status and path; nothing is mutated before the
+  // whole reply is known to fit
+  std::vector<int32_t> status(n, OK);
+  std::vector<int64_t> host_len(n, 4);
+  std::vector<uint32_t> host_cnt(n, 0);
+  std::vector<Watcher*> ws(n, nullptr);
+  int64_t nrefs = 0;
+  for (size_t i = 0; i < n; ++i) {
+    auto it = watchers_.find(wids[i]);
+    if (it == watchers_.end()) { status[i] = WATCH_DROPPED; host_len[i] = 0; continue; }
+    Watcher& w = it->second;
+    ws[i] = &w;
+    if (w.dropped || refsStale(w)) { status[i] = WATCH_DROPPED; host_len[i] = 0; continue; }
+    if (w.prefs.empty()) continue;  // section = u32 0
+    bool dev = pay_armed_ && w.prefix.size() <= (size_t)KEYW;
+    if (dev) {
+      // oldest delivered event of the oldest ref must still be resident
+      const PendRef& pr = w.prefs.front();
+      int64_t first = pr.base;
+      for (int c = 0; c < 8; ++c)
+        if (pr.words[c]) { first = pr.base + c * 64 + __builtin_ctzll(pr.words[c]); break; }
+      dev = first >= pay_.oldest_seq;
+    }
+    if (dev) {
+      host_len[i] = -1;
+      nrefs += (int64_t)w.prefs.size();
+    } else {
+      host_len[i] = (int64_t)wireSize(w, &host_cnt[i]);
+    }
+  }
+
+  // device sizing: flat ref table in watcher order, then deque order
+  std::vector<kbwpoll::PlanRef> prefs((size_t)nrefs);
+  if (nrefs > 0) {
+    kbslab::WpollRef* tab = slab_->WpollRefStaging(nrefs, &err);
+    if (!tab) return INTERNAL;
+    int64_t r = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (host_len[i] >= 0) continue;
+      for (const PendRef& pr : ws[i]->prefs) {
+        kbslab::WpollRef& t = tab[r++];
+        t.base = pr.base;
+        t.count = pr.count;
+        t.widx = (int32_t)i;
+        memcpy(t.words, pr.words, sizeof(t.words));
+      }
+    }
+    const kbslab::WpollSize* sizes = nullptr;
+    if (!slab_->WpollSizeRefs(nrefs, &sizes, &err)) return INTERNAL;
+    for (int64_t k = 0; k < nrefs; ++k)
+      prefs[(size_t)k] = kbwpoll::PlanRef{sizes[k].bytes, sizes[k].count, tab[k].widx};
+  }
+
+  kbwpoll::PlanOut plan;
+  int prc = kbwpoll::Plan(prefs.data(), (size_t)nrefs, status.data(),
+                          host_len.data(), n, cap, &plan);
+  if (prc != kbwpoll::P_OK && prc != kbwpoll::P_ENOBUF) {
+    err = "wpoll: reply section exceeds the u32 length field";
+    return INTERNAL;
+  }
+  *out_len = (size_t)plan.required;
+  if (prc == kbwpoll::P_ENOBUF) return NOBUF;  // every queue intact
+
+  // reply assembly: device sections arrive with one D2H into the pinned
+  // reply; the host then writes the directory, the count fields and the
+  // host-path sections into the same buffer, and one memcpy hands it over.
+  // With no device ref the host serializes straight into the caller's buffer.
+  uint8_t* reply = out;
+  if (nrefs > 0) {
+    uint64_t* offs = slab_->WpollOffStaging(nrefs, &err);
+    if (!offs) return INTERNAL;
+    memcpy(offs, plan.ref_off.data(), (size_t)nrefs * 8);
+    if (!slab_->WpollEmit(nrefs, (int64_t)plan.dev_lo, (int64_t)plan.dev_hi,
+                          (int64_t)plan.required, &reply, &err)) {
+      return INTERNAL;
+    }
+  }
+  kbwpoll::WriteDirectory(reply, status.data(), n, plan);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (status[i] != OK) continue;
+    uint8_t* sec = reply + plan.sec_off[i];
+    if (host_len[i] < 0) {
+      if ((int64_t)plan.count[i] != ws[i]->pend_events) {
+        // the device columns disagree with the host's delivery count: fail
+        // loudly (nothing drained) instead of handing out a short section
+        err = "wpoll: device event count mismatch";
+        return INTERNAL;
+      }
+      memcpy(sec, &plan.count[i], 4);
+      total += plan.count[i];
+      slab_->perf.wpoll_events_dev += plan.count[i];
+    } else if (!ws[i]->prefs.empty()) {
+      wireEmit(*ws[i], sec);
+      total += host_cnt[i];
+      slab_->perf.wpoll_events_host += host_cnt[i];
+    } else {
+      memset(sec, 0, 4);
+    }
+  }
+  if (reply != out) copyReply(out, reply, (size_t)plan.required);
+  if (total_events) *total_events = total;
+
+  // drain: the reply is complete, so every polled watcher's queue empties
+  // and dropped watchers go away exactly as in WatchPollWire
+  for (size_t i = 0; i < n; ++i) {
+    if (!ws[i]) continue;
+    if (status[i] == OK) {
+      ws[i]->prefs.clear();
+      ws[i]->pend_events = 0;
+    } else {
+      releaseSlot(*ws[i]);
+      watchers_.erase(wids[i]);
+    }
+  }
   return OK;
 }
 
@@ -1589,9 +1862,12 @@ bool Store::BenchDel(const uint8_t* dbuf, size_t n, uint64_t* out_revs,
 
 std::string Store::PerfJson() {
   const kbslab::Perf& p = slab_->perf;
-  char buf[1536];
+  char buf[2560];
   snprintf(buf, sizeof(buf),
-           "{\"scan_ms\":%.3f,\"gather_ms\":%.3f,\"get_ms\":%.3f,"
+           "{\"wpoll_ms\":%.3f,\"wpoll_d2h_ms\":%.3f,\"wpoll_launches\":%lld,"
+           "\"wpoll_events_dev\":%lld,\"wpoll_events_host\":%lld,"
+           "\"wpoll_bytes\":%lld,"
+           "\"scan_ms\":%.3f,\"gather_ms\":%.3f,\"get_ms\":%.3f,"
            "\"compact_ms\":%.3f,\"merge_ms\":%.3f,\"filter_ms\":%.3f,"
            "\"pack_d2h_ms\":%.3f,\"scan_launches\":%lld,\"rows_scanned\":%lld,"
            "\"bytes_gathered\":%lld,\"winners\":%lld,\"merges\":%lld,"
@@ -1601,6 +1877,9 @@ std::string Store::PerfJson() {
            "\"dbg\":[%.1f,%.1f,%.1f,%.1f,%.1f],"
            "\"ops\":{\"create\":%lld,\"update\":%lld,\"delete\":%lld,"
            "\"range\":%lld}}",
+           p.wpoll_ms, p.wpoll_d2h_ms, (long long)p.wpoll_launches,
+           (long long)p.wpoll_events_dev, (long long)p.wpoll_events_host,
+           (long long)p.wpoll_bytes,
            p.scan_ms, p.gather_ms, p.get_ms, p.compact_ms, p.merge_ms,
            p.filter_ms, p.pack_d2h_ms, (long long)p.scan_launches,
            (long long)p.rows_scanned, (long long)p.bytes_gathered,

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "slab_dev.h"
+#include "wpoll.h"
 
 namespace kbstore {
 
@@ -96,6 +97,12 @@ class Store {
   // returns NOBUF (need_bytes = required size) with the queue intact
   std::vector<Event> WatchPollLimited(int64_t wid, size_t max_bytes,
                                       size_t* need_bytes, Status* st);
+  // batched poll (kb_watch_poll_batch): n watchers in one call, sections
+  // serialized on the device from the payload ring; reply =
+  // u32 n; n x {i32 status; u32 len; len bytes}. NOBUF drains nothing.
+  Status WatchPollBatch(const int64_t* wids, size_t n, uint8_t* out, size_t cap,
+                        size_t* out_len, uint64_t* total_events,
+                        std::string* err = nullptr);
   void WatchCancel(int64_t wid);
 
   void ClockAdvance(int64_t secs);
@@ -217,6 +224,18 @@ class Store {
   // materialize a watcher's pending refs from the host ring; false if any
   // ref was overwritten (slow consumer fell behind the ring window)
   bool materializeRefs(Watcher& w, std::vector<Event>* out);
+  // wire size + event count of a watcher's pending refs / their bytes, the
+  // host serializer of the batched poll (same bytes as WatchPollWire)
+  size_t wireSize(const Watcher& w, uint32_t* count) const;
+  uint8_t* wireEmit(const Watcher& w, uint8_t* p) const;
+  bool refsStale(const Watcher& w) const;
+  // device payload ring: armed by the first WatchPollBatch; from then on
+  // pumpEvents pushes every event's wire record next to EventRingPush
+  int64_t pay_cfg_bytes_ = 256ll << 20;  // KB_WATCH_PAYLOAD_BYTES (0 = off)
+  bool pay_armed_ = false;
+  kbwpoll::PayRing pay_;
+  bool armPayload(std::string* err);
+  bool pushPayloads(size_t b0, int64_t count, int64_t base_seq, std::string* err);
   std::unordered_map<int64_t, Watcher> watchers_;
   std::vector<int64_t> free_slots_;
   int64_t next_slot_ = 0, next_wid_ = 1;
