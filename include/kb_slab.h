@@ -213,6 +213,17 @@ int kb_bench_range(kb_store*, const uint8_t* qbuf, size_t nq, int mode,
                    unsigned long long* total_kvs, double* secs);
 /* wait for in-flight pipelined D2H copies */
 int kb_sync(kb_store*);
+/* test hook: records of the most recent Range batch (kb_bench_range /
+ * kb_bench_step; for nq > 1024 the last 1024-query sub-batch). Collects a
+ * pending pipelined batch and drains in-flight D2H first. Launches no kernel.
+ * src 0 = per-query device arena (plain D2H of each query's region);
+ * src 1 = the pinned host buffer that batch's pipelined D2H filled
+ *         (error if the batch ran without mode bit 1).
+ * out: u32 nq; nq x {i64 written; i64 total; i64 bytes; i32 overflow; i32 0};
+ *      then, in query order, `bytes` record bytes of each non-overflowed
+ *      query (u64 rev | u32 klen | u32 vlen | key pad16 | value pad16).
+ * KB_ENOBUF with *out_len = needed size when cap is too small. */
+int kb_test_last_range(kb_store*, int src, uint8_t* out, size_t cap, size_t* out_len);
 /* batched conditional updates (txn.go:249-265); tbuf = n × {u32 klen;
  * u64 prev_rev; u32 vlen; key; val}; out_revs[i] = new revision or 0 on CAS
  * failure */

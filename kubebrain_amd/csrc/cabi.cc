@@ -353,6 +353,19 @@ int kb_sync(kb_store* h) {
   return 0;
 }
 
+int kb_test_last_range(kb_store* h, int src, uint8_t* out, size_t cap,
+                       size_t* out_len) {
+  std::string wire, err;
+  if (!((Store*)h)->TestLastRange(src, &wire, &err)) {
+    set_err(KB_EINTERNAL, err);
+    return KB_EINTERNAL;
+  }
+  *out_len = wire.size();
+  if (wire.size() > cap) return KB_ENOBUF;
+  memcpy(out, wire.data(), wire.size());
+  return KB_OK;
+}
+
 int kb_bench_txn(kb_store* h, const uint8_t* tbuf, size_t n, uint64_t* out_revs) {
   std::string err;
   if (!((Store*)h)->BenchTxn(tbuf, n, out_revs, &err)) {

@@ -1549,6 +1549,15 @@ struct Slab::Impl {
   bool cp_busy[2] = {false, false};
   int pk_idx = 0;
   double* pack_ms_acc = nullptr;  // -> perf.pack_d2h_ms (set by Slab)
+  Perf* perf = nullptr;           // -> Slab::perf (mergeRuns branch counters)
+  bool validate_dn = false;       // KB_VALIDATE_DN: re-check async predictions
+  // what the most recent RangeBatchFinish left behind (kb_test_last_range):
+  // its counters stay in h_resmeta, its records in d_gbuf and, for a
+  // pipelined d2h batch, in h_packs[last_slot]
+  int last_nq = 0;
+  int64_t last_qcap = 0;
+  bool last_pipe = false;
+  int last_slot = 0;
 
   bool ensure_pipe(int idx, int64_t need, std::string* err) {
     if (!cstream) {
@@ -1701,6 +1710,7 @@ struct Slab::Impl {
                  int64_t m, Col& dst, int64_t* out_n, std::string* err,
                  bool device_newn_ok = false) {
     if (n + m <= 2048) {  // single-launch path only where one CU wins
+      perf->merge_small++;
       hipLaunchKernelGGL(k_merge_small, dim3(1), dim3(256), 0, stream,
                          src.run(), n, dnew, m, spillA,
                          dst.keys, dst.meta, dst.rev, dst.vo, dst.ko,
@@ -1715,6 +1725,7 @@ struct Slab::Impl {
     if (m > 0 && m <= 1024 && n > 0) {
       // inverted small-insert path (the per-step txn merge): m searches into
       // the n-row run, not n searches into the m new rows
+      perf->merge_insert++;
       if (!d_outpos) HIP_CHECK(hipMalloc(&d_outpos, 1024 * 8));
       HIP_CHECK(hipMemsetAsync(s_a, 0, (n + 2) * 8, stream));
       HIP_CHECK(hipMemsetAsync(s_b, 0, n * 8, stream));
@@ -1744,6 +1755,7 @@ struct Slab::Impl {
       // big inverted path (folds, bulk appends): m*log2(n) probes + two
       // prefix sums + streaming scatters (the forward n*log2(m) rank path
       // paid ~400M random probes for a 20.7M x 512k fold and is gone).
+      perf->merge_big++;
       if (!ensure_mergebuf(m, err)) return false;
       HIP_CHECK(hipMemsetAsync(s_a, 0, (n + 2) * 8, stream));
       HIP_CHECK(hipMemsetAsync(s_b, 0, n * 8, stream));
@@ -1776,6 +1788,7 @@ struct Slab::Impl {
       return true;
     }
     // n == 0 here (every caller guards m > 0; n > 0 took the inverted path)
+    perf->merge_empty++;
     HIP_CHECK(hipMemsetAsync(s_c, 0, 8, stream));
     if (m > 0) {
       int64_t mb = ceil_div(m, 256);
@@ -1828,6 +1841,8 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   Slab* s = new Slab();
   s->p = new Impl();
   Impl* I = s->p;
+  I->perf = &s->perf;
+  I->validate_dn = env_i64("KB_VALIDATE_DN", 0) != 0;
   I->device = device < 0 ? 0 : device;
   I->max_rows = max_rows;
   I->heap_cap = heap_cap;
@@ -2020,9 +2035,7 @@ bool Slab::AppendRows(const uint8_t* keys, const uint64_t* meta,
     known_new_dn = -1;
     if (m > I->delta_cap) { if (err) *err = "append larger than delta cap"; return false; }
   }
-  static const bool validate = getenv("KB_VALIDATE_DN") &&
-                               atoi(getenv("KB_VALIDATE_DN")) != 0;
-  bool async = known_new_dn >= 0 && !validate;
+  bool async = known_new_dn >= 0 && !I->validate_dn;
   if (!async) HIP_CHECK(hipEventRecord(I->ev0, I->stream));
   if (!I->ensure_delta(m, err)) return false;
   {
@@ -2064,6 +2077,7 @@ bool Slab::AppendRows(const uint8_t* keys, const uint64_t* meta,
     // NOTE: the host `keys/meta/rev/vo` buffers were consumed by the H2D
     // copies above, which HIP stages synchronously for pageable memory.
     perf.merges++;
+    perf.merges_async++;
     std::swap(I->DA, I->DB);
     I->dn = known_new_dn;
     return true;
@@ -2098,6 +2112,7 @@ bool Slab::Fold(std::string* err) {
   (void)hipEventElapsedTime(&ms, I->ev2, I->ev3);
   perf.merge_ms += ms;
   perf.merges++;
+  perf.folds++;
   std::swap(I->A, I->B);
   I->n = new_n;
   I->dn = 0;
@@ -2242,6 +2257,9 @@ bool Slab::RangeBatchFinish(int nq, bool d2h, bool parse,
   if (nq == 0) return true;
   int64_t qcap = I->arena_bytes / nq;
   qcap &= ~15ll;
+  I->last_nq = nq;
+  I->last_qcap = qcap;
+  I->last_pipe = d2h && !parse;
   // small result metadata: d_found/d_total/d_gbytes are CONTIGUOUS slices of
   // one allocation (see Create), so one D2H covers them; ovf+counters ride
   // two more copies
@@ -2324,8 +2342,11 @@ bool Slab::RangeBatchFinish(int nq, bool d2h, bool parse,
     I->pack_ms_acc = &perf.pack_d2h_ms;
     int idx = I->pk_idx;
     I->pk_idx ^= 1;
-    if (!I->ensure_pipe(idx, acc, err)) return false;
+    // wait first: ensure_pipe may free this slot's pinned buffer, which the
+    // slot's previous copy could still be writing
     I->wait_slot(idx);
+    if (!I->ensure_pipe(idx, acc, err)) return false;
+    I->last_slot = idx;
     HIP_CHECK(hipMemcpyAsync(I->d_goffs, goffs.data(), (nq + 1) * 8,
                              hipMemcpyHostToDevice, I->stream));
     hipLaunchKernelGGL(k_pack, dim3(nq), dim3(256), 0, I->stream, I->d_gbuf,
@@ -2400,6 +2421,65 @@ bool Slab::DrainD2H(std::string* err) {
   p->pack_ms_acc = &perf.pack_d2h_ms;
   p->wait_slot(0);
   p->wait_slot(1);
+  return true;
+}
+
+bool Slab::LastRangeWire(int src, std::string* wire, std::string* err) {
+  Impl* I = p;
+  const int nq = I->last_nq;
+  if (src != 0 && src != 1) { if (err) *err = "last range: bad src"; return false; }
+  if (src == 1 && nq > 0 && !I->last_pipe) {
+    if (err) *err = "last range: the batch ran without d2h (mode bit 1)";
+    return false;
+  }
+  if (!DrainD2H(err)) return false;
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  const uint8_t* hm = I->h_resmeta;
+  std::vector<int64_t> found(nq), total(nq), gbytes(nq), goffs(nq + 1);
+  std::vector<int32_t> ovf(nq);
+  if (nq > 0) {
+    memcpy(found.data(), hm, nq * 8);
+    memcpy(total.data(), hm + I->max_q * 8, nq * 8);
+    memcpy(gbytes.data(), hm + I->max_q * 16, nq * 8);
+    memcpy(ovf.data(), hm + I->max_q * 24, nq * 4);
+  }
+  int64_t acc = 0;
+  for (int q = 0; q < nq; ++q) {
+    if (!ovf[q] && (gbytes[q] < 0 || gbytes[q] > I->last_qcap)) {
+      if (err) *err = "last range: corrupt byte count";
+      return false;
+    }
+    goffs[q] = acc;
+    acc += ovf[q] ? 0 : gbytes[q];
+  }
+  goffs[nq] = acc;
+  if (src == 1 && acc > I->h_packs_cap[I->last_slot]) {
+    if (err) *err = "last range: pinned buffer smaller than the batch";
+    return false;
+  }
+  wire->assign(4 + (size_t)nq * 32 + (size_t)acc, '\0');
+  uint8_t* w = (uint8_t*)&(*wire)[0];
+  uint32_t nq32 = (uint32_t)nq;
+  memcpy(w, &nq32, 4);
+  for (int q = 0; q < nq; ++q) {
+    uint8_t* e = w + 4 + (size_t)q * 32;
+    int32_t o = ovf[q] ? 1 : 0, z = 0;
+    memcpy(e, &found[q], 8);
+    memcpy(e + 8, &total[q], 8);
+    memcpy(e + 16, &gbytes[q], 8);
+    memcpy(e + 24, &o, 4);
+    memcpy(e + 28, &z, 4);
+  }
+  uint8_t* body = w + 4 + (size_t)nq * 32;
+  for (int q = 0; q < nq; ++q) {
+    if (ovf[q] || gbytes[q] == 0) continue;
+    if (src == 1) {
+      memcpy(body + goffs[q], I->h_packs[I->last_slot] + goffs[q], gbytes[q]);
+    } else {
+      HIP_CHECK(hipMemcpy(body + goffs[q], I->d_gbuf + (int64_t)q * I->last_qcap,
+                          gbytes[q], hipMemcpyDeviceToHost));
+    }
+  }
   return true;
 }
 

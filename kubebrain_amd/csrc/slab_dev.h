@@ -120,6 +120,12 @@ struct Perf {
   double wpoll_ms = 0, wpoll_d2h_ms = 0;
   int64_t wpoll_launches = 0, wpoll_events_dev = 0, wpoll_events_host = 0,
           wpoll_bytes = 0;
+  // which mergeRuns branch ran (k_merge_small / k_merge_insert_inv /
+  // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
+  // async no-sync branch, and delta->base folds: the tests prove with these
+  // that a workload reached the path it claims to cover
+  int64_t merge_small = 0, merge_insert = 0, merge_big = 0, merge_empty = 0,
+          merges_async = 0, folds = 0;
 };
 
 // batched watch poll: one delivery bitmap reference (<= 512 events of the
@@ -201,6 +207,11 @@ class Slab {
   bool RangeBatchFinish(int nq, bool d2h, bool parse,
                         std::vector<RangeResult>* outs, std::string* err);
   bool DrainD2H(std::string* err);
+  // TEST HOOK (kb_test_last_range): the records of the most recent
+  // RangeBatchFinish in the wire format documented in include/kb_slab.h.
+  // src 0 reads each query's region of the device arena, src 1 the pinned
+  // buffer the pipelined D2H of that batch filled. Launches no kernel.
+  bool LastRangeWire(int src, std::string* wire, std::string* err);
 
   // batched MVCC point read (range.go:91-121 reverse-iter semantics).
   // GetBatchEx(values=false) skips the value copy (meta-only: found/rev/

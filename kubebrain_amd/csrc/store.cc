@@ -1553,6 +1553,12 @@ bool Store::Sync(std::string* err) {
   return slab_->DrainD2H(err);
 }
 
+bool Store::TestLastRange(int src, std::string* wire, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  if (!finishPendingBench(nullptr, err)) return false;
+  return slab_->LastRangeWire(src, wire, err);
+}
+
 bool Store::BenchStep(const uint8_t* qbuf, size_t nq, const uint8_t* tbuf,
                       size_t ntx, int mode, uint64_t* out_revs,
                       unsigned long long* total, double* secs,
@@ -1873,6 +1879,9 @@ std::string Store::PerfJson() {
            "\"bytes_gathered\":%lld,\"winners\":%lld,\"merges\":%lld,"
            "\"compacts\":%lld,\"filter_launches\":%lld,\"filter_events\":%lld,"
            "\"filter_watchers\":%lld,\"slab_rows\":%lld,\"heap_used\":%lld,"
+           "\"merge_small\":%lld,\"merge_insert\":%lld,\"merge_big\":%lld,"
+           "\"merge_empty\":%lld,\"merges_async\":%lld,\"folds\":%lld,"
+           "\"base_rows\":%lld,\"delta_rows\":%lld,"
            "\"delivered\":%lld,\"sync_s\":%.3f,\"syncs\":%lld,"
            "\"dbg\":[%.1f,%.1f,%.1f,%.1f,%.1f],"
            "\"ops\":{\"create\":%lld,\"update\":%lld,\"delete\":%lld,"
@@ -1886,7 +1895,12 @@ std::string Store::PerfJson() {
            (long long)p.winners, (long long)p.merges, (long long)p.compacts,
            (long long)p.filter_launches, (long long)p.filter_events,
            (long long)p.filter_watchers, (long long)slab_->rows(),
-           (long long)slab_->heap_used(), (long long)delivered_,
+           (long long)slab_->heap_used(),
+           (long long)p.merge_small, (long long)p.merge_insert,
+           (long long)p.merge_big, (long long)p.merge_empty,
+           (long long)p.merges_async, (long long)p.folds,
+           (long long)slab_->rows(), (long long)slab_->delta_rows(),
+           (long long)delivered_,
            sync_s_, (long long)sync_n_,
            p.dbg_a, p.dbg_b, p.dbg_c, p.dbg_d, p.dbg_e,
            (long long)ops_create_,

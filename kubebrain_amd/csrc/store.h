@@ -133,6 +133,9 @@ class Store {
                  unsigned long long* total, double* secs, std::string* err);
   // wait for in-flight pipelined D2H copies (call before reading wall-clock)
   bool Sync(std::string* err);
+  // test hook (kb_test_last_range): collects a pending pipelined batch,
+  // drains in-flight D2H, then returns the last Range batch's records
+  bool TestLastRange(int src, std::string* wire, std::string* err);
   std::string PerfJson();
   void PerfReset();
 
