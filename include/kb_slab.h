@@ -83,6 +83,49 @@ int kb_get(kb_store*, const uint8_t* key, size_t klen, uint64_t rev,
 int kb_list(kb_store*, const uint8_t* start, size_t slen, const uint8_t* end,
             size_t elen, uint64_t rev, int64_t limit, uint8_t* out, size_t cap,
             size_t* out_len, uint64_t* header_rev, int* more);
+/* n Lists in one call (range.go:124-174 per query), one mutex hold.
+ * qbuf = n x {u32 slen; u32 elen; u64 rev; i64 limit; start; end} — the blob
+ * kb_bench_range takes. rev == 0 means latest, limit <= 0 unbounded.
+ * out = u32 n; n x {i32 status; i32 more; u64 header_rev; u64 len}; then the n
+ * sections in query order. For status KB_OK the len section bytes are EXACTLY
+ * what kb_list would have written for that query alone (u32 count; count x
+ * {u64 rev; u32 klen; key; u32 vlen; val}) and `more` is kb_list's. For any
+ * other status len = 0 and the status is kb_list's for that query
+ * (KB_EINVALID, KB_EBADKEY, KB_EKEYTOOLONG, KB_ECOMPACTED): one bad query
+ * never fails the call. header_rev is the committed revision at the call,
+ * the same in every entry; rev == 0 resolves to it.
+ * flags bit 0 = keys_only: every record carries vlen = 0 and no value bytes
+ * (kb_bench_range mode bit 2 semantics). Any other bit: KB_EINVALID.
+ * KB_ENOBUF: *out_len = required size of the whole reply, nothing is written,
+ * and the same call with a larger buffer returns the same bytes.
+ * n == 0 is valid (out = u32 0); n above KB_MAX_Q is served in sub-batches
+ * inside the call. *total_kvs = sum of the sections' counts.
+ * Sections are serialized by HIP kernels straight from the scan's winner rows
+ * (DESIGN.md §3.6); a query whose answer the winner table (KB_MAX_CAP rows)
+ * or the arena cannot hold whole is served by kb_list's own path with
+ * identical bytes. May be interleaved freely with every other call; a
+ * pending pipelined kb_bench_step batch is collected first. The call reuses
+ * the gather arena, so kb_test_last_range reports an EMPTY batch (u32 0)
+ * after a kb_list_batch until the next kb_bench_range / kb_bench_step. */
+int kb_list_batch(kb_store*, const uint8_t* qbuf, size_t n, int flags,
+                  uint8_t* out, size_t cap, size_t* out_len,
+                  unsigned long long* total_kvs);
+/* TEST-ONLY: the pure host reply planner of kb_list_batch (no GPU, no
+ * store). Per query: status; host_len (>= 4 = size of a host-serialized
+ * section, < 0 = device path whose section is 4 + dev_bytes); group (may be
+ * NULL) = scan sub-batch of a device query; arena_bytes bounds the reply span
+ * of one emit round (whole queries, one group). Outputs (caller arrays, may be
+ * NULL): per query the directory len, the reply offset of its section and its
+ * emit round (-1 = none); round_span = {lo, hi} reply offsets per round (room
+ * for n pairs); *n_rounds; *required = reply size = 4 + 24 n + sum of lens.
+ * Returns KB_OK, KB_ENOBUF (required > cap) or KB_EINVALID (an OK host
+ * section under 4 bytes, or a device section larger than the arena). */
+int kb_test_list_plan(const int* status, const long long* host_len,
+                      const unsigned long long* dev_bytes, const int* group,
+                      size_t n, size_t cap, unsigned long long arena_bytes,
+                      unsigned long long* dir_len, unsigned long long* sec_off,
+                      int* round, unsigned long long* round_span,
+                      size_t* n_rounds, size_t* required);
 /* backend.Count (range.go:177-205) */
 int kb_count(kb_store*, const uint8_t* start, size_t slen, const uint8_t* end,
              size_t elen, uint64_t* header_rev, uint64_t* count);

@@ -229,6 +229,82 @@ func (b *amdBackend) List(ctx context.Context, r *proto.RangeRequest) (*proto.Ra
 		Kvs: decodeKvs(out[:outLen]), More: more != 0}, nil
 }
 
+// ListResult is one query's share of a batched List: Err is what List would
+// have returned for that query alone (nil, or the error of KB_EINVALID /
+// KB_EBADKEY / KB_EKEYTOOLONG / KB_ECOMPACTED), Resp its decoded section.
+type ListResult struct {
+	Err  error
+	Resp *proto.RangeResponse
+}
+
+// ListBatch serves many RangeRequests with ONE kb_list_batch call: one mutex
+// hold, one header revision, the sections serialized on the GPU straight from
+// the scan's winner rows (DESIGN.md §3.6). A host that serves many concurrent
+// clients collects their pending Ranges and calls this from one goroutine in
+// place of one List per client. keysOnly drops the value bytes (etcd3
+// RangeRequest.KeysOnly). Same ENOBUF grow-and-retry contract as every other
+// call: a too-small buffer writes nothing and out_len carries the need. buf
+// may be nil; the (possibly grown) buffer is returned for reuse.
+// Not part of the Backend interface, and like the rest of this file it has
+// not been seen by a Go compiler (see the NOTE at the top); the executable
+// specification of the request and reply formats is kubebrain_amd/client.py
+// encode_queries / list_batch + tests/test_gpu_list_batch.py.
+func (b *amdBackend) ListBatch(reqs []*proto.RangeRequest, keysOnly bool, buf []byte) ([]ListResult, []byte, error) {
+	if len(buf) < 4 {
+		buf = make([]byte, 16<<20)
+	}
+	// qbuf = n x {u32 slen; u32 elen; u64 rev; i64 limit; start; end}
+	qbuf := make([]byte, 0, 64*len(reqs)+1)
+	for _, r := range reqs {
+		var h [24]byte
+		binary.LittleEndian.PutUint32(h[0:], uint32(len(r.Key)))
+		binary.LittleEndian.PutUint32(h[4:], uint32(len(r.End)))
+		binary.LittleEndian.PutUint64(h[8:], r.Revision)
+		binary.LittleEndian.PutUint64(h[16:], uint64(r.Limit))
+		qbuf = append(qbuf, h[:]...)
+		qbuf = append(qbuf, r.Key...)
+		qbuf = append(qbuf, r.End...)
+	}
+	qbuf = append(qbuf, 0) // never a nil pointer, even for zero queries
+	flags := C.int(0)
+	if keysOnly {
+		flags = 1
+	}
+	for {
+		var outLen C.size_t
+		var total C.ulonglong
+		rc := C.kb_list_batch(b.h, bptr(qbuf), C.size_t(len(reqs)), flags,
+			bptr(buf), C.size_t(len(buf)), &outLen, &total)
+		if rc == C.KB_ENOBUF { // nothing written; out_len carries need
+			buf = make([]byte, int(outLen))
+			continue
+		}
+		if rc != C.KB_OK {
+			return nil, buf, statusToErr(rc)
+		}
+		// reply = u32 n; n x {i32 status; i32 more; u64 header_rev; u64 len};
+		// then the n sections in query order
+		n := int(binary.LittleEndian.Uint32(buf))
+		off := 4 + 24*n
+		out := make([]ListResult, 0, n)
+		for i := 0; i < n; i++ {
+			d := buf[4+24*i:]
+			st := C.int(int32(binary.LittleEndian.Uint32(d)))
+			more := binary.LittleEndian.Uint32(d[4:]) != 0
+			hdr := binary.LittleEndian.Uint64(d[8:])
+			ln := int(binary.LittleEndian.Uint64(d[16:]))
+			if st != C.KB_OK {
+				out = append(out, ListResult{Err: statusToErr(st)})
+				continue
+			}
+			out = append(out, ListResult{Resp: &proto.RangeResponse{
+				Header: header(hdr), Kvs: decodeKvs(buf[off : off+ln]), More: more}})
+			off += ln
+		}
+		return out, buf, nil
+	}
+}
+
 func (b *amdBackend) Count(ctx context.Context, r *proto.CountRequest) (*proto.CountResponse, error) {
 	var hdr, cnt C.uint64_t
 	rc := C.kb_count(b.h, bptr(r.Key), C.size_t(len(r.Key)),

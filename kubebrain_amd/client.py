@@ -165,6 +165,51 @@ class Store:
         return RangeResp(rc, hr.value, _parse_kvs(self.buf[:out_len.value]),
                          bool(more.value))
 
+    @staticmethod
+    def encode_queries(queries) -> bytes:
+        """The query blob kb_list_batch and kb_bench_range share: per query
+        (start, end, rev, limit) -> {u32 slen; u32 elen; u64 rev; i64 limit;
+        start; end}."""
+        return b"".join(struct.pack("<IIQq", len(s), len(e), rev, limit) + s + e
+                        for s, e, rev, limit in queries)
+
+    def list_batch(self, queries, keys_only: bool = False):
+        """Many Lists in one call (kb_list_batch; product ABI only). queries =
+        [(start, end, rev, limit), ...]. Returns (rc, [(status, RangeResp),
+        ...], raw_sections) in query order; raw_sections[i] holds the section's
+        bytes exactly as kb_list would have written them (b"" for a non-OK
+        status). KB_ENOBUF is handled here by growing the buffer and repeating
+        the call (the failed attempt wrote nothing)."""
+        n = len(queries)
+        qbuf = self.encode_queries(queries)
+        out_len = C.c_size_t(); total = C.c_ulonglong()
+        f = self._f("list_batch")
+        buf, cap = self.buf, self.BUF
+        for _ in range(4):
+            rc = f(C.c_void_p(self.h), qbuf, C.c_size_t(n),
+                   C.c_int(1 if keys_only else 0), buf, C.c_size_t(cap),
+                   C.byref(out_len), C.byref(total))
+            if rc != ENOBUF:
+                break
+            cap = out_len.value
+            buf = C.create_string_buffer(cap)
+        if rc != OK:
+            return rc, [], []
+        raw = C.string_at(buf, out_len.value)
+        (cnt,) = struct.unpack_from("<I", raw, 0)
+        assert cnt == n, (cnt, n)
+        off = 4 + 24 * n
+        res, sections = [], []
+        for i in range(n):
+            st, more, hr, ln = struct.unpack_from("<iiQQ", raw, 4 + 24 * i)
+            sec = raw[off:off + ln]; off += ln
+            sections.append(sec)
+            res.append((st, RangeResp(st, hr, _parse_kvs(sec) if st == OK else [],
+                                      bool(more))))
+        assert off == len(raw), (off, len(raw))
+        assert sum(len(r.kvs) for _, r in res) == total.value
+        return rc, res, sections
+
     def count(self, start: bytes, end: bytes):
         hr = C.c_uint64(); cnt = C.c_uint64()
         rc = self._f("count")(C.c_void_p(self.h), start, C.c_size_t(len(start)), end,

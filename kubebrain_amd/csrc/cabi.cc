@@ -171,6 +171,51 @@ int kb_list(kb_store* h, const uint8_t* start, size_t slen, const uint8_t* end,
   return st;
 }
 
+int kb_list_batch(kb_store* h, const uint8_t* qbuf, size_t n, int flags,
+                  uint8_t* out, size_t cap, size_t* out_len,
+                  unsigned long long* total_kvs) {
+  std::string err;
+  size_t len = 0;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->ListBatch(qbuf, n, flags, out, cap, &len, &total,
+                                     &err);
+  if (out_len) *out_len = len;
+  if (total_kvs) *total_kvs = total;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
+int kb_test_list_plan(const int* status, const long long* host_len,
+                      const unsigned long long* dev_bytes, const int* group,
+                      size_t n, size_t cap, unsigned long long arena_bytes,
+                      unsigned long long* dir_len, unsigned long long* sec_off,
+                      int* round, unsigned long long* round_span,
+                      size_t* n_rounds, size_t* required) {
+  std::vector<int32_t> st(status, status + n);
+  std::vector<int64_t> hl(host_len, host_len + n);
+  std::vector<uint64_t> db(dev_bytes, dev_bytes + n);
+  std::vector<int32_t> gr;
+  if (group) gr.assign(group, group + n);
+  kblist::PlanOut o;
+  int rc = kblist::Plan(st.data(), hl.data(), db.data(),
+                        group ? gr.data() : nullptr, n, cap, arena_bytes, &o);
+  if (rc != KB_OK && rc != KB_ENOBUF) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (dir_len) dir_len[i] = o.len[i];
+    if (sec_off) sec_off[i] = o.sec_off[i];
+    if (round) round[i] = o.round[i];
+  }
+  // round_span holds up to n {lo, hi} pairs (a round has at least one query)
+  for (size_t r = 0; r < o.round_lo.size() && round_span; ++r) {
+    round_span[2 * r] = o.round_lo[r];
+    round_span[2 * r + 1] = o.round_hi[r];
+  }
+  if (n_rounds) *n_rounds = o.round_lo.size();
+  if (required) *required = (size_t)o.required;
+  return rc;
+}
+
 int kb_count(kb_store* h, const uint8_t* start, size_t slen, const uint8_t* end,
              size_t elen, uint64_t* header_rev, uint64_t* count) {
   Status st;

@@ -1333,6 +1333,136 @@ __global__ __launch_bounds__(256) void k_wpoll_emit(
   }
 }
 
+// ---- batched List (kb_list_batch) -------------------------
+// The scan is k_range_bounds + k_range_scan2 unchanged (cap = limit+1): the
+// tagged winner rows of query q sit in rows_m[q*max_cap ..], found_out[q] of
+// them. k_list_size turns them into wire sizes, k_list_emit into wire bytes
+// {u64 rev; u32 klen; key; u32 vlen; val} packed back to back.
+
+// one 256-thread block per query: the first min(found, limit) winners, one
+// meta word each (8 B per winner, no key or value column), exclusive wire
+// offsets by wave scans chained through LDS
+__global__ __launch_bounds__(256) void k_list_size(
+    Run b, Run d, int64_t n, int64_t dn,
+    const uint64_t* __restrict__ rows_m, int64_t max_cap,
+    const int64_t* __restrict__ found_out,
+    const int64_t* __restrict__ total_out,
+    const DevRangeQ* __restrict__ qs, int nq,
+    uint64_t* __restrict__ offs, ListSize* __restrict__ out) {
+  const int q = blockIdx.x;
+  if (q >= nq) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint64_t wsum[4];
+  int64_t found = found_out[q];
+  if (found < 0) found = 0;
+  if (found > max_cap) found = max_cap;
+  const int64_t cap = qs[q].cap;  // limit+1; <= 0 unbounded
+  const bool more = cap > 0 && found >= cap;      // range.go:168-171
+  const int64_t take = more ? cap - 1 : found;    // the cut to `limit`
+  // the table held the whole answer unless List's own continuation test
+  // (written >= cap || total > written) fires for an unbounded query, or
+  // the cap never fitted the table
+  const bool partial = cap > 0 ? cap > max_cap
+                               : (found >= max_cap || total_out[q] > found);
+  const bool konly = qs[q].keys_only != 0;
+  const uint64_t* rows = rows_m + (int64_t)q * max_cap;
+  uint64_t* qoffs = offs + (int64_t)q * max_cap;
+  uint64_t base = 0;  // block-uniform running section size
+  for (int64_t c0 = 0; c0 < take; c0 += 256) {
+    const int64_t j = c0 + threadIdx.x;
+    uint64_t sz = 0;
+    if (j < take) {
+      const uint64_t rt = rows[j];
+      const bool isd = (rt & ROW_TAG_DELTA) != 0;
+      const int64_t row = (int64_t)(rt & ROW_MASK);
+      if (row < (isd ? dn : n)) {
+        const uint64_t m = (isd ? d.meta : b.meta)[row];
+        sz = 16 + (uint64_t)meta_klen(m) + (konly ? 0 : meta_vlen(m));
+      }
+    }
+    const uint64_t incl = wp_scan64(sz, lane);
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint64_t woff = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < w) woff += wsum[k];
+      tot += wsum[k];
+    }
+    if (j < take) qoffs[j] = base + woff + incl - sz;
+    base += tot;
+    __syncthreads();  // wsum reused by the next chunk
+  }
+  if (threadIdx.x == 0) {
+    ListSize s;
+    s.bytes = base;
+    s.count = (uint32_t)take;
+    s.flags = (more ? LS_MORE : 0) | (partial ? LS_PARTIAL : 0);
+    out[q] = s;
+  }
+}
+
+// one wave per winner record, flat over the round's records: wave g finds
+// its query by a binary search over cum[] (records before each query), so
+// skewed batches leave no idle blocks. The destination sec_base[q] + offs is
+// arbitrarily aligned (the wire is packed); the three sources (96 B key
+// column row, key-spill tail, value heap) are 16 B aligned and padded to 16,
+// which is what wp_copy_record needs. Store-hazard rule of §3.5: nothing
+// wider than a byte leaves [dst, dst+reclen); the 12+4 header bytes go out
+// as byte stores. A record that would leave the arena, or whose source lies
+// outside the run / heap, is skipped, never written.
+__global__ __launch_bounds__(256) void k_list_emit(
+    Run rb, Run rd, int64_t n, int64_t dn,
+    const uint8_t* __restrict__ spill, int64_t spill_used,
+    const uint8_t* __restrict__ heap, int64_t heap_used,
+    const uint64_t* __restrict__ rows_m, int64_t max_cap,
+    const DevRangeQ* __restrict__ qs, int nq,
+    const uint64_t* __restrict__ offs, const uint64_t* __restrict__ sec_base,
+    const uint64_t* __restrict__ cum, uint8_t* __restrict__ arena,
+    int64_t arena_cap) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= cum[nq]) return;  // wave-uniform
+  int lo = 0, hi = nq;       // cum[lo] <= g < cum[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int q = lo;
+  const uint64_t j = g - cum[q];
+  if (j >= (uint64_t)max_cap) return;
+  const uint64_t rt = rows_m[(int64_t)q * max_cap + (int64_t)j];
+  const bool isd = (rt & ROW_TAG_DELTA) != 0;
+  const int64_t row = (int64_t)(rt & ROW_MASK);
+  if (row >= (isd ? dn : n)) return;
+  const Run& r = isd ? rd : rb;
+  const uint64_t m = r.meta[row];
+  const uint32_t klen = meta_klen(m);
+  const uint32_t vlen = qs[q].keys_only ? 0 : meta_vlen(m);
+  const uint64_t dd = sec_base[q] + offs[(int64_t)q * max_cap + (int64_t)j];
+  const uint64_t reclen = 16 + (uint64_t)klen + vlen;
+  if (dd > (uint64_t)arena_cap || reclen > (uint64_t)arena_cap - dd) return;
+  uint8_t* dst = arena + dd;
+  const uint64_t rev = r.rev[row];
+  if (lane < 8) dst[lane] = (uint8_t)(rev >> (8 * lane));
+  else if (lane < 12) dst[lane] = (uint8_t)(klen >> (8 * (lane - 8)));
+  else if (lane < 16) dst[klen + lane] = (uint8_t)(vlen >> (8 * (lane - 12)));
+  const uint32_t kin = klen > (uint32_t)KEYW ? (uint32_t)KEYW : klen;
+  wp_copy_record(r.keys + row * KEYW, dst + 12, kin, lane);
+  if (klen > (uint32_t)KEYW) {  // spill tail (keys > 96B)
+    const uint64_t ko = r.ko[row];
+    const uint32_t tl = klen - (uint32_t)KEYW;
+    if ((ko & 15) == 0 && ko + ((tl + 15) & ~15u) <= (uint64_t)spill_used)
+      wp_copy_record(spill + ko, dst + 12 + KEYW, tl, lane);
+  }
+  if (vlen) {
+    const uint64_t vo = r.vo[row];
+    if ((vo & 15) == 0 &&
+        vo + (((uint64_t)vlen + 15) & ~15ull) <= (uint64_t)heap_used)
+      wp_copy_record(heap + vo, dst + 16 + klen, vlen, lane);
+  }
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -1515,6 +1645,34 @@ struct Slab::Impl {
     return true;
   }
 
+  // batched List (allocated on first use): per-query sizes, the emit plan
+  // (base[max_q] | cum[max_q+1]) and the pinned reply
+  ListSize *h_lsizes = nullptr, *d_lsizes = nullptr;
+  uint64_t *h_lplan = nullptr, *d_lplan = nullptr;
+  uint8_t* h_lreply = nullptr;
+  int64_t lreply_cap = 0;
+  int list_nq = 0;  // queries of the resident sized sub-batch
+  hipEvent_t ev_l0 = nullptr, ev_l1 = nullptr, ev_l2 = nullptr;
+  void free_list() {
+    for (void* q : {(void*)d_lsizes, (void*)d_lplan})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_lsizes, (void*)h_lplan, (void*)h_lreply})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_l0, ev_l1, ev_l2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_list(std::string* err) {
+    if (d_lsizes) return true;
+    HIP_CHECK(hipEventCreate(&ev_l0));
+    HIP_CHECK(hipEventCreate(&ev_l1));
+    HIP_CHECK(hipEventCreate(&ev_l2));
+    HIP_CHECK(hipHostMalloc(&h_lsizes, (int64_t)max_q * sizeof(ListSize) + 8));
+    HIP_CHECK(hipHostMalloc(&h_lplan, (int64_t)(2 * max_q + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_lplan, (int64_t)(2 * max_q + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_lsizes, (int64_t)max_q * sizeof(ListSize)));
+    return true;
+  }
+
   // KB_SCAN_DBG=1: per-phase wall_clock64 cycle sums from k_range_scan2
   // ([0]=bounds [1]=pass1a [2]=pass1b [3]=scatter [4]=merge [5]=block total)
   unsigned long long* d_dbg = nullptr;
@@ -1621,6 +1779,7 @@ struct Slab::Impl {
       if (p) (void)hipFree(p);
     }
     free_wpoll();
+    free_list();
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_resmeta) (void)hipHostFree(h_resmeta);
     for (int i = 0; i < 2; ++i) {
@@ -2179,15 +2338,13 @@ bool Slab::RangeBatch(const std::vector<DevRangeQ>& qs, bool d2h,
   return RangeBatchEx(qs, d2h, true, outs, err, qtails);
 }
 
-bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
-                           const std::string& qtails) {
+bool Slab::RangeScanStart(const std::vector<DevRangeQ>& qs, std::string* err,
+                          const std::string& qtails) {
   Impl* I = p;
   int nq = (int)qs.size();
   if (kb_trace()) fprintf(stderr, "[trace] RBStart nq=%d cap0=%lld\n", nq, nq?(long long)qs[0].cap:-1);
   if (nq == 0) return true;
   if (nq > I->max_q) { if (err) *err = "too many queries per batch (KB_MAX_Q)"; return false; }
-  int64_t qcap = I->arena_bytes / nq;
-  qcap &= ~15ll;
   if (!I->ensure_qtails(qtails, err)) return false;
   {
     // pinned double-buffered query upload (a 900-query batch is ~200 KB;
@@ -2218,6 +2375,17 @@ bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
                      I->d_total, I->d_scanned, I->d_bounds4, I->shadow,
                      I->d_dbg);
   HIP_CHECK(hipEventRecord(I->ev1, I->stream));
+  return true;
+}
+
+bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
+                           const std::string& qtails) {
+  Impl* I = p;
+  int nq = (int)qs.size();
+  if (!RangeScanStart(qs, err, qtails)) return false;
+  if (nq == 0) return true;
+  int64_t qcap = I->arena_bytes / nq;
+  qcap &= ~15ll;
   hipLaunchKernelGGL(k_gather, dim3(nq), dim3(256), 0, I->stream, I->A.run(),
                      I->DA.run(), I->heapA, I->d_rowsm, I->max_cap,
                      I->d_found, I->d_qs, nq, I->d_gbuf, qcap, I->d_offs,
@@ -2480,6 +2648,121 @@ bool Slab::LastRangeWire(int src, std::string* wire, std::string* err) {
                           gbytes[q], hipMemcpyDeviceToHost));
     }
   }
+  return true;
+}
+
+// ---- batched List (kb_list_batch) -----------------------------------------
+
+int Slab::max_queries() const { return p->max_q; }
+int64_t Slab::arena_bytes() const { return p->arena_bytes; }
+void Slab::ForgetLastRange() { p->last_nq = 0; }
+
+bool Slab::ListSizeBatch(const std::vector<DevRangeQ>& qs,
+                         const std::string& qtails, const ListSize** sizes,
+                         std::string* err) {
+  Impl* I = p;
+  const int nq = (int)qs.size();
+  I->list_nq = 0;
+  if (nq <= 0 || nq > I->max_q) {
+    if (err) *err = "list batch: bad sub-batch size (KB_MAX_Q)";
+    return false;
+  }
+  if (!I->ensure_list(err)) return false;
+  // the arena stops holding gathered records once an emit round runs
+  I->last_nq = 0;
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  if (!RangeScanStart(qs, err, qtails)) return false;
+  HIP_CHECK(hipEventRecord(I->ev_l0, I->stream));
+  hipLaunchKernelGGL(k_list_size, dim3(nq), dim3(256), 0, I->stream,
+                     I->A.run(), I->DA.run(), I->n, I->dn, I->d_rowsm,
+                     I->max_cap, I->d_found, I->d_total, I->d_qs, nq,
+                     (uint64_t*)I->d_offs, I->d_lsizes);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_l1, I->stream));
+  // the one small readback: 16 B per query (+ the scan's row counter)
+  HIP_CHECK(hipMemcpyAsync(I->h_lsizes, I->d_lsizes, nq * sizeof(ListSize),
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipMemcpyAsync((uint8_t*)I->h_lsizes + (int64_t)I->max_q * sizeof(ListSize),
+                           I->d_scanned, 8, hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev0, I->ev1);
+  perf.scan_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_l0, I->ev_l1);
+  perf.list_ms += ms;
+  perf.scan_launches++;
+  unsigned long long scanned = 0;
+  memcpy(&scanned, (uint8_t*)I->h_lsizes + (int64_t)I->max_q * sizeof(ListSize), 8);
+  perf.rows_scanned += (int64_t)scanned;
+  I->list_nq = nq;
+  *sizes = I->h_lsizes;
+  return true;
+}
+
+uint8_t* Slab::ListReply(int64_t total, std::string* err) {
+  Impl* I = p;
+  if (total > I->lreply_cap) {
+    if (I->h_lreply) (void)hipHostFree(I->h_lreply);
+    I->h_lreply = nullptr;
+    I->lreply_cap = 0;
+    int64_t cap = std::max<int64_t>(1 << 20, total + total / 2);
+    HIP_CHECK_NULL(hipHostMalloc(&I->h_lreply, cap));
+    I->lreply_cap = cap;
+  }
+  return I->h_lreply;
+}
+
+bool Slab::ListPlanStaging(uint64_t** base, uint64_t** cum, std::string* err) {
+  Impl* I = p;
+  if (!I->ensure_list(err)) return false;
+  *base = I->h_lplan;
+  *cum = I->h_lplan + I->max_q;
+  return true;
+}
+
+bool Slab::ListEmit(int nq, int64_t span, uint8_t* reply, int64_t reply_off,
+                    std::string* err) {
+  Impl* I = p;
+  if (!I->d_lsizes || nq <= 0 || nq != I->list_nq || span < 0 ||
+      span > I->arena_bytes || reply != I->h_lreply || reply_off < 0 ||
+      reply_off + span > I->lreply_cap) {
+    if (err) *err = "list batch: no resident sub-batch or bad emit span";
+    return false;
+  }
+  const uint64_t* cum = I->h_lplan + I->max_q;
+  const uint64_t nrec = cum[nq];
+  if (nrec > (uint64_t)nq * (uint64_t)I->max_cap) {
+    if (err) *err = "list batch: emit plan names more records than the table holds";
+    return false;
+  }
+  HIP_CHECK(hipMemcpyAsync(I->d_lplan, I->h_lplan, (int64_t)(2 * I->max_q + 1) * 8,
+                           hipMemcpyHostToDevice, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_l0, I->stream));
+  if (nrec > 0) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_list_emit, dim3((uint32_t)ceil_div((int64_t)nrec, 4)),
+                       dim3(256), 0, I->stream, I->A.run(), I->DA.run(), I->n,
+                       I->dn, I->spillA, I->spill_used_, I->heapA,
+                       I->heap_used_, I->d_rowsm, I->max_cap, I->d_qs, nq,
+                       (const uint64_t*)I->d_offs, I->d_lplan,
+                       I->d_lplan + I->max_q, I->d_gbuf, I->arena_bytes);
+    HIP_CHECK(hipGetLastError());
+    perf.list_emit_launches++;
+  }
+  HIP_CHECK(hipEventRecord(I->ev_l1, I->stream));
+  if (nrec > 0 && span > 0)
+    HIP_CHECK(hipMemcpyAsync(reply + reply_off, I->d_gbuf, span,
+                             hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_l2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_l0, I->ev_l1);
+  perf.list_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_l1, I->ev_l2);
+  perf.list_d2h_ms += ms;
+  if (nrec > 0) perf.list_batch_bytes += span;
   return true;
 }
 

@@ -120,6 +120,11 @@ struct Perf {
   double wpoll_ms = 0, wpoll_d2h_ms = 0;
   int64_t wpoll_launches = 0, wpoll_events_dev = 0, wpoll_events_host = 0,
           wpoll_bytes = 0;
+  // batched List (kb_list_batch): k_list_size + k_list_emit kernel time, the
+  // section D2H, queries per path, kvs and device bytes moved
+  double list_ms = 0, list_d2h_ms = 0;
+  int64_t list_batch_calls = 0, list_batch_q_dev = 0, list_batch_q_host = 0,
+          list_batch_kvs = 0, list_batch_bytes = 0, list_emit_launches = 0;
   // which mergeRuns branch ran (k_merge_small / k_merge_insert_inv /
   // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
   // async no-sync branch, and delta->base folds: the tests prove with these
@@ -146,6 +151,16 @@ struct WpollSize {
 };
 // one contiguous piece of a payload push: staging bytes -> byte-ring offset
 struct PaySeg { int64_t ring_off, stage_off, len; };
+// batched List (kb_list_batch): k_list_size result per query
+struct ListSize {
+  uint64_t bytes;  // wire bytes of the records (without the u32 count)
+  uint32_t count;  // records = min(found, limit)
+  uint32_t flags;  // LS_MORE | LS_PARTIAL
+};
+constexpr uint32_t LS_MORE = 1;     // kb_list's `more` (found > limit)
+constexpr uint32_t LS_PARTIAL = 2;  // the winner table did not hold the whole
+                                    // answer: the host path must serve it
+static_assert(sizeof(ListSize) == 16, "list size entry layout");
 
 
 
@@ -207,6 +222,34 @@ class Slab {
   bool RangeBatchFinish(int nq, bool d2h, bool parse,
                         std::vector<RangeResult>* outs, std::string* err);
   bool DrainD2H(std::string* err);
+  // batched List (kb_list_batch). RangeScanStart is the scan
+  // half of RangeBatchStart alone (k_range_bounds + k_range_scan2): tagged
+  // winner rows per query, no gather. ListSizeBatch runs it, then k_list_size
+  // (per-winner wire offsets into the offsets scratch, per-query ListSize)
+  // and reads back 16 B per query; *sizes points into pinned memory valid
+  // until the next call. The sized sub-batch stays resident for ListEmit.
+  int max_queries() const;     // KB_MAX_Q
+  int64_t arena_bytes() const; // KB_ARENA_BYTES: bounds one emit round
+  bool RangeScanStart(const std::vector<DevRangeQ>& qs, std::string* err,
+                      const std::string& qtails = std::string());
+  bool ListSizeBatch(const std::vector<DevRangeQ>& qs,
+                     const std::string& qtails, const ListSize** sizes,
+                     std::string* err);
+  // pinned reply buffer of >= total bytes; contents survive until the next
+  // call with a larger total
+  uint8_t* ListReply(int64_t total, std::string* err);
+  // pinned per-query emit plan the host fills in place: base[max_q] = arena
+  // offset of a query's first record, cum[max_q+1] = records emitted before
+  // query q in this round (a query outside the round adds none)
+  bool ListPlanStaging(uint64_t** base, uint64_t** cum, std::string* err);
+  // one emit round over the resident sub-batch: k_list_emit writes the
+  // staged queries' records into the arena, then arena [0, span) arrives at
+  // reply + reply_off with one D2H
+  bool ListEmit(int nq, int64_t span, uint8_t* reply, int64_t reply_off,
+                std::string* err);
+  // kb_test_last_range reports an empty batch from here on (the arena no
+  // longer holds gathered records)
+  void ForgetLastRange();
   // TEST HOOK (kb_test_last_range): the records of the most recent
   // RangeBatchFinish in the wire format documented in include/kb_slab.h.
   // src 0 reads each query's region of the device arena, src 1 the pinned

@@ -1275,6 +1275,215 @@ RangeResponse Store::List(const Bytes& start, const Bytes& end,
   return resp;
 }
 
+// kb_list_batch: n Lists under one mutex hold. Phase 1 sizes
+// every query (scan + k_list_size per sub-batch of <= KB_MAX_Q queries, the
+// host path for what the winner table cannot hold whole), the planner lays
+// out the reply and decides ENOBUF, phase 2 emits the wire bytes on the
+// device round by round. Only one sub-batch's winner table is resident, so a
+// sub-batch that was displaced between the phases (a later sub-batch or a
+// host-path List ran) is scanned and sized again: same mutex hold, same
+// device state, same sizes.
+Status Store::ListBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                        size_t cap, size_t* out_len, uint64_t* total_kvs,
+                        std::string* errp) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  *out_len = 0;
+  if (total_kvs) *total_kvs = 0;
+  if ((flags & ~1) != 0 || n > 0x7fffffffull) return INVALID_ARG;
+  std::string errl;
+  std::string& err = errp ? *errp : errl;
+  if (!syncReads(&err)) return INTERNAL;
+  kbslab::Perf& perf = slab_->perf;
+  perf.list_batch_calls++;
+  const bool konly = (flags & 1) != 0;
+  const uint64_t hdr = committed_;
+  const int64_t max_cap = slab_->max_winner_cap();
+  const uint64_t arena = (uint64_t)slab_->arena_bytes();
+  const size_t max_q = (size_t)slab_->max_queries();
+
+  struct Q { Bytes start, end; uint64_t rev; int64_t limit; };
+  std::vector<Q> qs(n);
+  std::vector<int32_t> status(n, OK), more(n, 0), group(n, -1);
+  std::vector<int64_t> host_len(n, 0);  // >= 4: host section; < 0: device
+  std::vector<uint64_t> dev_bytes(n, 0);
+  std::vector<uint32_t> cnt(n, 0);
+  std::vector<Bytes> host_sec(n);
+  std::vector<std::vector<size_t>> groups;  // device candidates per sub-batch
+  std::vector<size_t> host_q;
+  {
+    const uint8_t* p = qbuf;
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t slen, elen;
+      memcpy(&slen, p, 4); p += 4;
+      memcpy(&elen, p, 4); p += 4;
+      memcpy(&qs[i].rev, p, 8); p += 8;
+      memcpy(&qs[i].limit, p, 8); p += 8;
+      qs[i].start.assign((const char*)p, slen); p += slen;
+      qs[i].end.assign((const char*)p, elen); p += elen;
+      // per-query status exactly as List decides it
+      const Q& q = qs[i];
+      if (q.end.empty()) { status[i] = INVALID_ARG; continue; }
+      Status bv = validateBound(q.start);
+      if (bv == OK) bv = validateBound(q.end);
+      if (bv != OK) { status[i] = bv; continue; }
+      if (q.rev == 0) qs[i].rev = hdr;
+      if (q.start >= q.end) { status[i] = INVALID_ARG; continue; }
+      Status cst = checkCompactRace(qs[i].rev);
+      if (cst != OK) { status[i] = cst; continue; }
+      if (q.limit > 0 && q.limit >= max_cap) {  // limit+1 > the winner table
+        host_q.push_back(i);
+        continue;
+      }
+      if (groups.empty() || groups.back().size() >= max_q) groups.emplace_back();
+      group[i] = (int32_t)groups.size() - 1;
+      groups.back().push_back(i);
+    }
+  }
+
+  std::vector<DevRangeQ> dq;
+  std::string qtails;
+  int resident = -1;  // sub-batch whose winner table + offsets are on the device
+  auto sizeGroup = [&](size_t g, const kbslab::ListSize** sizes) {
+    const std::vector<size_t>& mem = groups[g];
+    dq.assign(mem.size(), DevRangeQ{});
+    qtails.clear();
+    for (size_t k = 0; k < mem.size(); ++k) {
+      const Q& q = qs[mem[k]];
+      DevRangeQ& d = dq[k];
+      setBound(d.start, &d.start_klen, &d.start_ko, q.start, &qtails);
+      setBound(d.end, &d.end_klen, &d.end_ko, q.end, &qtails);
+      d.read_rev = q.rev;
+      d.start_rev = 0;
+      d.cap = q.limit > 0 ? q.limit + 1 : 0;  // range.go:154-158
+      d.count_only = 0;
+      d.keys_only = konly ? 1 : 0;
+    }
+    resident = -1;
+    if (!slab_->ListSizeBatch(dq, qtails, sizes, &err)) return false;
+    resident = (int)g;
+    return true;
+  };
+
+  // phase 1: sizes
+  for (size_t g = 0; g < groups.size(); ++g) {
+    const kbslab::ListSize* sizes = nullptr;
+    if (!sizeGroup(g, &sizes)) return INTERNAL;
+    for (size_t k = 0; k < groups[g].size(); ++k) {
+      const size_t i = groups[g][k];
+      if ((sizes[k].flags & kbslab::LS_PARTIAL) || 4 + sizes[k].bytes > arena) {
+        host_q.push_back(i);
+        continue;
+      }
+      host_len[i] = -1;
+      dev_bytes[i] = sizes[k].bytes;
+      cnt[i] = sizes[k].count;
+      more[i] = (sizes[k].flags & kbslab::LS_MORE) ? 1 : 0;
+    }
+  }
+  size_t ndev = 0;
+  for (size_t i = 0; i < n; ++i) ndev += status[i] == OK && host_len[i] < 0;
+  ops_range_ += (int64_t)ndev;
+  // host path: Store::List's chunked frontier loop, re-serialized to the
+  // same wire bytes (never changes the result, only the path)
+  for (size_t i : host_q) {
+    Status st;
+    RangeResponse r = List(qs[i].start, qs[i].end, qs[i].rev, qs[i].limit, &st);
+    resident = -1;
+    status[i] = st;
+    if (st != OK) continue;
+    size_t bytes = 4;
+    for (const KeyValue& kv : r.kvs)
+      bytes += kblist::RecordSize(kv.key.size(), konly ? 0 : kv.value.size());
+    Bytes& sec = host_sec[i];
+    sec.resize(bytes);
+    uint8_t* w = (uint8_t*)&sec[0];
+    uint32_t c32 = (uint32_t)r.kvs.size();
+    memcpy(w, &c32, 4);
+    w += 4;
+    for (const KeyValue& kv : r.kvs)
+      w = kblist::PutRecord(w, kv.revision, kv.key.data(), (uint32_t)kv.key.size(),
+                            kv.value.data(), konly ? 0 : (uint32_t)kv.value.size());
+    host_len[i] = (int64_t)bytes;
+    cnt[i] = c32;
+    more[i] = r.more ? 1 : 0;
+  }
+  if (!host_q.empty() || !groups.empty()) slab_->ForgetLastRange();
+
+  kblist::PlanOut plan;
+  int prc = kblist::Plan(status.data(), host_len.data(), dev_bytes.data(),
+                         group.data(), n, cap, arena, &plan);
+  if (prc != kblist::P_OK && prc != kblist::P_ENOBUF) {
+    err = "list batch: planner rejected the sized sections";
+    return INTERNAL;
+  }
+  *out_len = (size_t)plan.required;
+  if (prc == kblist::P_ENOBUF) return NOBUF;  // no emit kernel, no D2H ran
+
+  // phase 2: device sections arrive round by round in the pinned reply; the
+  // host then writes the directory, the counts and the host-path sections,
+  // and one copy hands the reply over. With no device section the host
+  // writes straight into the caller's buffer.
+  uint8_t* reply = out;
+  if (ndev > 0) {
+    reply = slab_->ListReply((int64_t)plan.required, &err);
+    if (!reply) return INTERNAL;
+    uint64_t *base = nullptr, *cum = nullptr;
+    if (!slab_->ListPlanStaging(&base, &cum, &err)) return INTERNAL;
+    for (size_t r = 0; r < plan.round_lo.size(); ++r) {
+      // the round's sub-batch = the group of any of its members
+      int g = -1;
+      uint64_t nrec = 0;
+      for (size_t i = 0; i < n; ++i)
+        if (plan.round[i] == (int32_t)r) { g = group[i]; nrec += cnt[i]; }
+      if (g < 0 || nrec == 0) continue;  // sections of u32 0 only: host-written
+      const std::vector<size_t>& mem = groups[(size_t)g];
+      if (resident != g) {
+        const kbslab::ListSize* sizes = nullptr;
+        if (!sizeGroup((size_t)g, &sizes)) return INTERNAL;
+        for (size_t k = 0; k < mem.size(); ++k) {
+          const size_t i = mem[k];
+          if (host_len[i] < 0 && (sizes[k].bytes != dev_bytes[i] ||
+                                  sizes[k].count != cnt[i])) {
+            err = "list batch: a re-sized sub-batch changed under the mutex";
+            return INTERNAL;
+          }
+        }
+      }
+      uint64_t acc = 0;
+      for (size_t k = 0; k < mem.size(); ++k) {
+        const size_t i = mem[k];
+        const bool in = plan.round[i] == (int32_t)r;
+        cum[k] = acc;
+        base[k] = in ? plan.sec_off[i] + 4 - plan.round_lo[r] : 0;
+        if (in) acc += cnt[i];
+      }
+      cum[mem.size()] = acc;
+      if (!slab_->ListEmit((int)mem.size(),
+                           (int64_t)(plan.round_hi[r] - plan.round_lo[r]), reply,
+                           (int64_t)plan.round_lo[r], &err))
+        return INTERNAL;
+    }
+  }
+  kblist::WriteDirectory(reply, status.data(), more.data(), hdr, n, plan);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (status[i] != OK) continue;
+    uint8_t* sec = reply + plan.sec_off[i];
+    if (host_len[i] < 0) {
+      memcpy(sec, &cnt[i], 4);
+      perf.list_batch_q_dev++;
+    } else {
+      memcpy(sec, host_sec[i].data(), host_sec[i].size());
+      perf.list_batch_q_host++;
+    }
+    total += cnt[i];
+  }
+  if (reply != out) copyReply(out, reply, (size_t)plan.required);
+  perf.list_batch_kvs += (int64_t)total;
+  if (total_kvs) *total_kvs = total;
+  return OK;
+}
+
 CountResponse Store::Count(const Bytes& start, const Bytes& end, Status* st) {
   // range.go:177-205
   std::lock_guard<std::recursive_mutex> lk(mu_);
@@ -1868,9 +2077,18 @@ bool Store::BenchDel(const uint8_t* dbuf, size_t n, uint64_t* out_revs,
 
 std::string Store::PerfJson() {
   const kbslab::Perf& p = slab_->perf;
-  char buf[2560];
-  snprintf(buf, sizeof(buf),
-           "{\"wpoll_ms\":%.3f,\"wpoll_d2h_ms\":%.3f,\"wpoll_launches\":%lld,"
+  char buf[3072];
+  int at = snprintf(buf, sizeof(buf),
+           "{\"list_batch_calls\":%lld,\"list_batch_q_dev\":%lld,"
+           "\"list_batch_q_host\":%lld,\"list_batch_kvs\":%lld,"
+           "\"list_batch_bytes\":%lld,\"list_emit_launches\":%lld,"
+           "\"list_ms\":%.3f,\"list_d2h_ms\":%.3f,\"gather_launches\":%lld,",
+           (long long)p.list_batch_calls, (long long)p.list_batch_q_dev,
+           (long long)p.list_batch_q_host, (long long)p.list_batch_kvs,
+           (long long)p.list_batch_bytes, (long long)p.list_emit_launches,
+           p.list_ms, p.list_d2h_ms, (long long)p.gather_launches);
+  snprintf(buf + at, sizeof(buf) - (size_t)at,
+           "\"wpoll_ms\":%.3f,\"wpoll_d2h_ms\":%.3f,\"wpoll_launches\":%lld,"
            "\"wpoll_events_dev\":%lld,\"wpoll_events_host\":%lld,"
            "\"wpoll_bytes\":%lld,"
            "\"scan_ms\":%.3f,\"gather_ms\":%.3f,\"get_ms\":%.3f,"

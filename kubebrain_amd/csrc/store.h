@@ -18,6 +18,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "lplan.h"
 #include "slab_dev.h"
 #include "wpoll.h"
 
@@ -69,6 +70,14 @@ class Store {
   GetResponse Get(const Bytes& key, uint64_t revision, Status* st);
   RangeResponse List(const Bytes& start, const Bytes& end, uint64_t revision,
                      int64_t limit, Status* st);
+  // batched List (kb_list_batch): n queries under one mutex hold, sections
+  // serialized on the device from the scan's winner rows;
+  // qbuf = the kb_bench_range query blob, reply = u32 n; n x {i32 status;
+  // i32 more; u64 header_rev; u64 len}; then the sections. NOBUF writes
+  // nothing past cap (*out_len = required size).
+  Status ListBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                   size_t cap, size_t* out_len, uint64_t* total_kvs,
+                   std::string* err = nullptr);
   CountResponse Count(const Bytes& start, const Bytes& end, Status* st);
   uint64_t Compact(uint64_t revision, Status* st);
   uint64_t GetCurrentRevision();
