@@ -126,6 +126,51 @@ int kb_test_list_plan(const int* status, const long long* host_len,
                       unsigned long long* dir_len, unsigned long long* sec_off,
                       int* round, unsigned long long* round_span,
                       size_t* n_rounds, size_t* required);
+/* n Gets in one call (range.go:34-121 per query), one mutex hold.
+ * qbuf = n x {u32 klen; u64 rev; key} — the blob kb_bench_del takes, with the
+ * read revision in place of prev_rev. rev == 0 means latest, as in kb_get.
+ * out = u32 n; n x {i32 status; i32 has_kv; u64 header_rev; u64 mod_rev;
+ * u64 vlen}; then the value bytes of every has_kv entry, back to back in
+ * query order, unpadded; vlen = the number of value bytes of that entry.
+ * status, has_kv, header_rev, mod_rev and the value of an entry are EXACTLY
+ * what kb_get(key, rev) would have returned at that moment: not found or a
+ * tombstone winner gives has_kv 0, mod_rev 0, vlen 0; header_rev =
+ * max(committed revision at the call, mod_rev). Like kb_get the call
+ * validates nothing about a key: one with bytes <= 0x24, an empty one or one
+ * longer than 4096 B is searched for as it is. A key may repeat in a batch.
+ * flags bit 0 = no_values: every entry has vlen = 0 and no bytes follow;
+ * has_kv and mod_rev stay real. Any other bit: KB_EINVALID.
+ * KB_ENOBUF: *out_len = required size of the whole reply, nothing is written,
+ * and the same call with a larger buffer returns the same bytes.
+ * n == 0 is valid (out = u32 0); n above KB_MAX_Q is served in sub-batches
+ * inside the call. *total_found = number of has_kv entries.
+ * The directory and the packed values are written by HIP kernels (DESIGN.md
+ * §3.7); a single value larger than the arena (KB_ARENA_BYTES) is copied from
+ * the value heap by the host with identical bytes. May be interleaved freely
+ * with every other call; a pending pipelined kb_bench_step batch is collected
+ * first. The call reuses the gather arena, so kb_test_last_range reports an
+ * EMPTY batch (u32 0) after a kb_get_batch with n > 0 until the next
+ * kb_bench_range / kb_bench_step. */
+int kb_get_batch(kb_store*, const uint8_t* qbuf, size_t n, int flags,
+                 uint8_t* out, size_t cap, size_t* out_len,
+                 unsigned long long* total_found);
+/* TEST-ONLY: the pure host reply planner of kb_get_batch (no GPU, no store).
+ * Per query has_kv and vlen (0 without has_kv); queries i / max_q form one
+ * sub-batch; arena_bytes bounds the value bytes of one emit round. Outputs
+ * (caller arrays, may be NULL): per query the reply offset of its value
+ * bytes and its emit round (-1 = no bytes, -2 = host path: one value larger
+ * than the arena); round_span = {lo, hi} query index range per round (room
+ * for n pairs; a round never spans two sub-batches or a host-path query);
+ * *n_rounds; *n_host; *required = reply size = 4 + 32 n + sum of vlen;
+ * *total_found = has_kv entries. Returns KB_OK, KB_ENOBUF (required > cap)
+ * or KB_EINVALID (max_q == 0, or vlen != 0 without has_kv). */
+int kb_test_get_plan(const int* has_kv, const unsigned long long* vlen,
+                     size_t n, size_t max_q, size_t cap,
+                     unsigned long long arena_bytes,
+                     unsigned long long* val_off, int* round,
+                     unsigned long long* round_span, size_t* n_rounds,
+                     size_t* n_host, size_t* required,
+                     unsigned long long* total_found);
 /* backend.Count (range.go:177-205) */
 int kb_count(kb_store*, const uint8_t* start, size_t slen, const uint8_t* end,
              size_t elen, uint64_t* header_rev, uint64_t* count);

@@ -305,6 +305,78 @@ func (b *amdBackend) ListBatch(reqs []*proto.RangeRequest, keysOnly bool, buf []
 	}
 }
 
+// GetQuery is one point read of a batched Get: Revision 0 means latest.
+type GetQuery struct {
+	Key      []byte
+	Revision uint64
+}
+
+// GetBatch serves many point reads with ONE kb_get_batch call: one mutex
+// hold, the reply's directory and the packed values written on the GPU
+// (DESIGN.md §3.7). Entry i is what Get(Key, Revision) would have returned
+// at that moment: no Kvs for a missing key or a tombstone. A host collects
+// the object GETs and the read-before-CAS lookups of its pending requests
+// and calls this from one goroutine. noValues drops the value bytes
+// (mod revisions stay real). Same ENOBUF grow-and-retry contract as every
+// other call: a too-small buffer writes nothing and out_len carries the
+// need. buf may be nil; the (possibly grown) buffer is returned for reuse.
+// Not part of the Backend interface, and like the rest of this file it has
+// not been seen by a Go compiler (see the NOTE at the top); the executable
+// specification of the request and reply formats is kubebrain_amd/client.py
+// encode_gets / get_batch + tests/test_gpu_get_batch.py.
+func (b *amdBackend) GetBatch(qs []GetQuery, noValues bool, buf []byte) ([]*proto.GetResponse, []byte, error) {
+	if len(buf) < 4 {
+		buf = make([]byte, 1<<20)
+	}
+	// qbuf = n x {u32 klen; u64 rev; key}
+	qbuf := make([]byte, 0, 48*len(qs)+1)
+	for _, q := range qs {
+		var h [12]byte
+		binary.LittleEndian.PutUint32(h[0:], uint32(len(q.Key)))
+		binary.LittleEndian.PutUint64(h[4:], q.Revision)
+		qbuf = append(qbuf, h[:]...)
+		qbuf = append(qbuf, q.Key...)
+	}
+	qbuf = append(qbuf, 0) // never a nil pointer, even for zero queries
+	flags := C.int(0)
+	if noValues {
+		flags = 1
+	}
+	for {
+		var outLen C.size_t
+		var found C.ulonglong
+		rc := C.kb_get_batch(b.h, bptr(qbuf), C.size_t(len(qs)), flags,
+			bptr(buf), C.size_t(len(buf)), &outLen, &found)
+		if rc == C.KB_ENOBUF { // nothing written; out_len carries need
+			buf = make([]byte, int(outLen))
+			continue
+		}
+		if rc != C.KB_OK {
+			return nil, buf, statusToErr(rc)
+		}
+		// reply = u32 n; n x {i32 status; i32 has_kv; u64 header_rev;
+		// u64 mod_rev; u64 vlen}; then the values in query order
+		n := int(binary.LittleEndian.Uint32(buf))
+		off := 4 + 32*n
+		out := make([]*proto.GetResponse, 0, n)
+		for i := 0; i < n; i++ {
+			d := buf[4+32*i:]
+			hasKv := binary.LittleEndian.Uint32(d[4:]) != 0
+			hdr := binary.LittleEndian.Uint64(d[8:])
+			mod := binary.LittleEndian.Uint64(d[16:])
+			vlen := int(binary.LittleEndian.Uint64(d[24:]))
+			resp := &proto.GetResponse{Header: header(hdr)}
+			if hasKv {
+				val := append([]byte(nil), buf[off:off+vlen]...)
+				resp.Kv = &proto.KeyValue{Key: qs[i].Key, Value: val, Revision: mod}
+			}
+			off += vlen
+			out = append(out, resp)
+		}
+		return out, buf, nil
+	}
+}
+
 func (b *amdBackend) Count(ctx context.Context, r *proto.CountRequest) (*proto.CountResponse, error) {
 	var hdr, cnt C.uint64_t
 	rc := C.kb_count(b.h, bptr(r.Key), C.size_t(len(r.Key)),

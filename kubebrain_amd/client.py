@@ -210,6 +210,50 @@ class Store:
         assert sum(len(r.kvs) for _, r in res) == total.value
         return rc, res, sections
 
+    @staticmethod
+    def encode_gets(queries) -> bytes:
+        """The query blob of kb_get_batch: per query (key, rev) ->
+        {u32 klen; u64 rev; key}. A bare key means rev 0 (latest)."""
+        qs = [(q, 0) if isinstance(q, (bytes, bytearray)) else q for q in queries]
+        return b"".join(struct.pack("<IQ", len(k), rev) + k for k, rev in qs)
+
+    def get_batch(self, queries, no_values: bool = False):
+        """Many Gets in one call (kb_get_batch; product ABI only). queries =
+        [(key, rev), ...] (or bare keys, rev 0). Returns (rc, [(status,
+        header_rev, Kv | None), ...], raw_reply) in query order: per entry
+        what get(key, rev) returns; with no_values every Kv carries b"".
+        KB_ENOBUF is handled here by growing the buffer and repeating the
+        call (the failed attempt wrote nothing)."""
+        qs = [(q, 0) if isinstance(q, (bytes, bytearray)) else q for q in queries]
+        n = len(qs)
+        qbuf = self.encode_gets(qs)
+        out_len = C.c_size_t(); total = C.c_ulonglong()
+        f = self._f("get_batch")
+        buf, cap = self.buf, self.BUF
+        for _ in range(4):
+            rc = f(C.c_void_p(self.h), qbuf, C.c_size_t(n),
+                   C.c_int(1 if no_values else 0), buf, C.c_size_t(cap),
+                   C.byref(out_len), C.byref(total))
+            if rc != ENOBUF:
+                break
+            cap = out_len.value
+            buf = C.create_string_buffer(cap)
+        if rc != OK:
+            return rc, [], b""
+        raw = C.string_at(buf, out_len.value)
+        (cnt,) = struct.unpack_from("<I", raw, 0)
+        assert cnt == n, (cnt, n)
+        off = 4 + 32 * n
+        res = []
+        for i, (key, _rev) in enumerate(qs):
+            st, has, hr, mod, vlen = struct.unpack_from("<iiQQQ", raw, 4 + 32 * i)
+            kv = Kv(bytes(key), raw[off:off + vlen], mod) if has else None
+            off += vlen
+            res.append((st, hr, kv))
+        assert off == len(raw), (off, len(raw))
+        assert sum(kv is not None for _, _, kv in res) == total.value
+        return rc, res, raw
+
     def count(self, start: bytes, end: bytes):
         hr = C.c_uint64(); cnt = C.c_uint64()
         rc = self._f("count")(C.c_void_p(self.h), start, C.c_size_t(len(start)), end,

@@ -216,6 +216,49 @@ int kb_test_list_plan(const int* status, const long long* host_len,
   return rc;
 }
 
+int kb_get_batch(kb_store* h, const uint8_t* qbuf, size_t n, int flags,
+                 uint8_t* out, size_t cap, size_t* out_len,
+                 unsigned long long* total_found) {
+  std::string err;
+  size_t len = 0;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->GetBatch(qbuf, n, flags, out, cap, &len, &total,
+                                    &err);
+  if (out_len) *out_len = len;
+  if (total_found) *total_found = total;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
+int kb_test_get_plan(const int* has_kv, const unsigned long long* vlen,
+                     size_t n, size_t max_q, size_t cap,
+                     unsigned long long arena_bytes,
+                     unsigned long long* val_off, int* round,
+                     unsigned long long* round_span, size_t* n_rounds,
+                     size_t* n_host, size_t* required,
+                     unsigned long long* total_found) {
+  std::vector<int32_t> hk(has_kv, has_kv + n);
+  std::vector<uint64_t> vl(vlen, vlen + n);
+  kbget::PlanOut o;
+  int rc = kbget::Plan(hk.data(), vl.data(), n, max_q, cap, arena_bytes, &o);
+  if (rc != KB_OK && rc != KB_ENOBUF) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (val_off) val_off[i] = o.val_off[i];
+    if (round) round[i] = o.round[i];
+  }
+  // round_span holds up to n {lo, hi} pairs (a round has at least one query)
+  for (size_t r = 0; r < o.round_lo.size() && round_span; ++r) {
+    round_span[2 * r] = o.round_lo[r];
+    round_span[2 * r + 1] = o.round_hi[r];
+  }
+  if (n_rounds) *n_rounds = o.round_lo.size();
+  if (n_host) *n_host = (size_t)o.n_host;
+  if (required) *required = (size_t)o.required;
+  if (total_found) *total_found = o.found;
+  return rc;
+}
+
 int kb_count(kb_store* h, const uint8_t* start, size_t slen, const uint8_t* end,
              size_t elen, uint64_t* header_rev, uint64_t* count) {
   Status st;

@@ -1463,6 +1463,147 @@ __global__ __launch_bounds__(256) void k_list_emit(
   }
 }
 
+// ---- batched point read (kb_get_batch) ---------------------
+// k_get_find resolves each query to a tagged row, k_get_plan turns the rows
+// into the reply's finished directory entries and per-query arena offsets,
+// k_get_emit packs the value bytes back to back in the arena. k_get2 and its
+// callers are not involved.
+
+constexpr uint64_t GET_ROW_NONE = ~0ull;  // no row (key, rev <= R) exists
+
+// one wave per query, four per block: the search of k_get2 (delta first,
+// then base; the delta run wins when it has any row of the key <= R)
+__global__ __launch_bounds__(256) void k_get_find(
+    Run b, Run d, int64_t n, int64_t dn, const uint8_t* __restrict__ spill,
+    const uint8_t* __restrict__ qtails, const DevGetQ* __restrict__ qs, int nq,
+    uint64_t* __restrict__ otag, uint64_t* __restrict__ orev,
+    uint64_t* __restrict__ ometa) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (q >= nq) return;  // wave-uniform
+  const DevGetQ& Q = qs[q];
+  const QKey qk{Q.key, Q.klen, Q.ko, qtails};
+  // upper_bound(key, R) == lower_bound(key, R + 1), saturating
+  const uint64_t nr = Q.read_rev == UINT64_MAX ? UINT64_MAX : Q.read_rev + 1;
+  uint64_t tag = GET_ROW_NONE;
+  if (dn > 0) {
+    const int64_t ub = d_lb_wave(d, spill, dn, qk, nr);
+    if (ub > 0 && d.rev[ub - 1] >= 1 && rowcmp_q(d, spill, ub - 1, qk) == 0)
+      tag = ROW_TAG_DELTA | (uint64_t)(ub - 1);
+  }
+  if (tag == GET_ROW_NONE) {
+    const int64_t ub = d_lb_wave(b, spill, n, qk, nr);
+    if (ub > 0 && b.rev[ub - 1] >= 1 && rowcmp_q(b, spill, ub - 1, qk) == 0)
+      tag = (uint64_t)(ub - 1);
+  }
+  if (lane != 0) return;
+  otag[q] = tag;
+  if (tag == GET_ROW_NONE) {
+    orev[q] = 0;
+    ometa[q] = 0;
+  } else {
+    const Run& r = (tag & ROW_TAG_DELTA) ? d : b;
+    const int64_t row = (int64_t)(tag & ROW_MASK);
+    orev[q] = r.rev[row];
+    ometa[q] = r.meta[row];
+  }
+}
+
+// one 256-thread block per sub-batch, 256 queries per pass: has_kv and vlen
+// per query, the exclusive scan of vlen (wave scans chained through LDS) as
+// arena offsets, and the reply's 32-byte directory entries in final form.
+// hdr = {u64 total; u64 skipped; nq x {i32 status; i32 has_kv; u64
+// header_rev; u64 mod_rev; u64 vlen}}; the skipped counter of k_get_emit is
+// zeroed here, one launch ahead of its first increment.
+__global__ __launch_bounds__(256) void k_get_plan(
+    const uint64_t* __restrict__ tag, const uint64_t* __restrict__ rev,
+    const uint64_t* __restrict__ meta, int nq, int no_values,
+    uint64_t committed, uint64_t* __restrict__ aoff,
+    uint64_t* __restrict__ hdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint64_t wsum[4];
+  uint64_t base = 0;  // block-uniform running total
+  for (int c0 = 0; c0 < nq; c0 += 256) {
+    const int q = c0 + threadIdx.x;
+    uint64_t vlen = 0, mod = 0;
+    bool has = false;
+    if (q < nq) {
+      const uint64_t m = meta[q];
+      has = tag[q] != GET_ROW_NONE && !(m & M_TOMB);
+      if (has) {
+        mod = rev[q];
+        vlen = no_values ? 0 : meta_vlen(m);
+      }
+    }
+    const uint64_t incl = wp_scan64(vlen, lane);
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint64_t woff = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < w) woff += wsum[k];
+      tot += wsum[k];
+    }
+    if (q < nq) {
+      aoff[q] = base + woff + incl - vlen;
+      uint64_t* e = hdr + 2 + 4 * (int64_t)q;
+      e[0] = (uint64_t)(has ? 1 : 0) << 32;  // status KB_OK | has_kv
+      e[1] = mod > committed ? mod : committed;
+      e[2] = mod;
+      e[3] = vlen;
+    }
+    base += tot;
+    __syncthreads();  // wsum reused by the next pass
+  }
+  if (threadIdx.x == 0) {
+    hdr[0] = base;
+    hdr[1] = 0;
+  }
+}
+
+// one 256-thread block per query: wave w copies the 4 KiB chunks w, w + 4,
+// ... of the value from the heap to arena + aoff[q]. vo is 16 B aligned and
+// the value padded to 16 in the heap, chunk starts are multiples of 16 from
+// there, so every chunk is a legal wp_copy_record call; its 16-byte stores
+// stay inside the chunk's own destination range and byte stores cover the
+// edges (§3.5 store-hazard rule: neighbouring values are other blocks').
+// A query with no bytes, a row or heap extent out of range, a misaligned vo
+// or a destination leaving the arena is skipped whole and counted.
+__global__ __launch_bounds__(256) void k_get_emit(
+    Run rb, Run rd, int64_t n, int64_t dn, const uint8_t* __restrict__ heap,
+    int64_t heap_used, const uint64_t* __restrict__ tag,
+    const uint64_t* __restrict__ aoff, const uint64_t* __restrict__ hdr,
+    int nq, uint8_t* __restrict__ arena, int64_t arena_cap,
+    unsigned long long* __restrict__ skipped) {
+  const int q = blockIdx.x;
+  if (q >= nq) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t vlen = hdr[2 + 4 * (int64_t)q + 3];
+  const uint64_t t = tag[q];
+  const uint64_t dd = aoff[q];
+  bool ok = vlen != 0 && t != GET_ROW_NONE;
+  uint64_t vo = 0;
+  if (ok) {
+    const bool isd = (t & ROW_TAG_DELTA) != 0;
+    const int64_t row = (int64_t)(t & ROW_MASK);
+    ok = row < (isd ? dn : n);
+    if (ok) vo = (isd ? rd.vo : rb.vo)[row];
+  }
+  ok = ok && (vo & 15) == 0 && vo <= (uint64_t)heap_used &&
+       ((vlen + 15) & ~15ull) <= (uint64_t)heap_used - vo &&
+       dd <= (uint64_t)arena_cap && vlen <= (uint64_t)arena_cap - dd;
+  if (!ok) {  // block-uniform
+    if (threadIdx.x == 0) atomicAdd(skipped, 1ull);
+    return;
+  }
+  const uint8_t* src = heap + vo;
+  uint8_t* dst = arena + dd;
+  for (uint64_t c = (uint64_t)w << 12; c < vlen; c += 4ull << 12) {
+    const uint64_t left = vlen - c;
+    wp_copy_record(src + c, dst + c, left < 4096 ? (uint32_t)left : 4096u, lane);
+  }
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -1673,6 +1814,38 @@ struct Slab::Impl {
     return true;
   }
 
+  // batched point read (allocated on first use): find results, arena
+  // offsets, the {total; skipped; directory} block and its pinned mirror,
+  // the pinned query upload mirror
+  uint64_t *d_gtag = nullptr, *d_grev = nullptr, *d_gmeta = nullptr,
+           *d_gaoff = nullptr, *d_ghdr = nullptr, *h_ghdr = nullptr;
+  DevGetQ* h_getq = nullptr;
+  int get_nq = 0;  // queries of the resident launch
+  hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr, ev_b2 = nullptr;
+  void free_getb() {
+    for (void* q : {(void*)d_gtag, (void*)d_grev, (void*)d_gmeta,
+                    (void*)d_gaoff, (void*)d_ghdr})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_ghdr, (void*)h_getq})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_b0, ev_b1, ev_b2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_getb(std::string* err) {
+    if (d_ghdr) return true;
+    HIP_CHECK(hipEventCreate(&ev_b0));
+    HIP_CHECK(hipEventCreate(&ev_b1));
+    HIP_CHECK(hipEventCreate(&ev_b2));
+    HIP_CHECK(hipHostMalloc(&h_ghdr, 16 + (int64_t)max_q * 32));
+    HIP_CHECK(hipHostMalloc(&h_getq, (int64_t)max_q * sizeof(DevGetQ)));
+    HIP_CHECK(hipMalloc(&d_gtag, (int64_t)max_q * 8));
+    HIP_CHECK(hipMalloc(&d_grev, (int64_t)max_q * 8));
+    HIP_CHECK(hipMalloc(&d_gmeta, (int64_t)max_q * 8));
+    HIP_CHECK(hipMalloc(&d_gaoff, (int64_t)max_q * 8));
+    HIP_CHECK(hipMalloc(&d_ghdr, 16 + (int64_t)max_q * 32));
+    return true;
+  }
+
   // KB_SCAN_DBG=1: per-phase wall_clock64 cycle sums from k_range_scan2
   // ([0]=bounds [1]=pass1a [2]=pass1b [3]=scatter [4]=merge [5]=block total)
   unsigned long long* d_dbg = nullptr;
@@ -1780,6 +1953,7 @@ struct Slab::Impl {
     }
     free_wpoll();
     free_list();
+    free_getb();
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_resmeta) (void)hipHostFree(h_resmeta);
     for (int i = 0; i < 2; ++i) {
@@ -2763,6 +2937,129 @@ bool Slab::ListEmit(int nq, int64_t span, uint8_t* reply, int64_t reply_off,
   (void)hipEventElapsedTime(&ms, I->ev_l1, I->ev_l2);
   perf.list_d2h_ms += ms;
   if (nrec > 0) perf.list_batch_bytes += span;
+  return true;
+}
+
+// ---- batched point read (kb_get_batch) ------------------------------------
+
+bool Slab::GetBatchLaunch(const DevGetQ* qs, int nq, const std::string& qtails,
+                          bool no_values, uint64_t committed,
+                          const GetBatchHdr** hdr, std::string* err) {
+  Impl* I = p;
+  I->get_nq = 0;
+  if (nq <= 0 || nq > I->max_q) {
+    if (err) *err = "get batch: bad sub-batch size (KB_MAX_Q)";
+    return false;
+  }
+  if (!I->ensure_getb(err)) return false;
+  if (!I->ensure_qtails(qtails, err)) return false;
+  // the arena stops holding gathered records once the emit runs
+  I->last_nq = 0;
+  memcpy(I->h_getq, qs, sizeof(DevGetQ) * (size_t)nq);
+  HIP_CHECK(hipMemcpyAsync(I->d_gq, I->h_getq, sizeof(DevGetQ) * (size_t)nq,
+                           hipMemcpyHostToDevice, I->stream));
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  HIP_CHECK(hipEventRecord(I->ev_b0, I->stream));
+  hipLaunchKernelGGL(k_get_find, dim3((uint32_t)ceil_div(nq, 4)), dim3(256), 0,
+                     I->stream, I->A.run(), I->DA.run(), I->n, I->dn,
+                     I->spillA, I->d_qtails, I->d_gq, nq, I->d_gtag,
+                     I->d_grev, I->d_gmeta);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_get_plan, dim3(1), dim3(256), 0, I->stream, I->d_gtag,
+                     I->d_grev, I->d_gmeta, nq, no_values ? 1 : 0, committed,
+                     I->d_gaoff, I->d_ghdr);
+  HIP_CHECK(hipGetLastError());
+  if (!no_values) {  // nothing to copy otherwise: every vlen is 0
+    hipLaunchKernelGGL(k_get_emit, dim3((uint32_t)nq), dim3(256), 0, I->stream,
+                       I->A.run(), I->DA.run(), I->n, I->dn, I->heapA,
+                       I->heap_used_, I->d_gtag, I->d_gaoff, I->d_ghdr, nq,
+                       I->d_gbuf, I->arena_bytes,
+                       (unsigned long long*)(I->d_ghdr + 1));
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(I->ev_b1, I->stream));
+  // the one small readback: total, skipped and 32 B per query
+  HIP_CHECK(hipMemcpyAsync(I->h_ghdr, I->d_ghdr, 16 + (int64_t)nq * 32,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_b2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_b0, I->ev_b1);
+  perf.get_batch_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_b1, I->ev_b2);
+  perf.get_batch_d2h_ms += ms;
+  perf.get_batch_launches++;
+  I->get_nq = nq;
+  *hdr = (const GetBatchHdr*)I->h_ghdr;
+  return true;
+}
+
+bool Slab::GetBatchFetch(int64_t span, uint8_t* reply, int64_t reply_off,
+                         std::string* err) {
+  Impl* I = p;
+  if (I->get_nq <= 0 || span <= 0 || span > I->arena_bytes ||
+      reply != I->h_lreply || reply_off < 0 ||
+      reply_off + span > I->lreply_cap) {
+    if (err) *err = "get batch: no resident launch or bad value span";
+    return false;
+  }
+  HIP_CHECK(hipEventRecord(I->ev_b1, I->stream));
+  HIP_CHECK(hipMemcpyAsync(reply + reply_off, I->d_gbuf, span,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_b2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_b1, I->ev_b2);
+  perf.get_batch_d2h_ms += ms;
+  perf.get_batch_bytes += span;
+  return true;
+}
+
+bool Slab::GetBatchHostValue(const DevGetQ& q, const std::string& qtails,
+                             uint64_t mod_rev, uint64_t vlen, uint8_t* dst,
+                             std::string* err) {
+  Impl* I = p;
+  I->get_nq = 0;  // the find results of the resident launch are overwritten
+  if (!I->ensure_getb(err)) return false;
+  if (!I->ensure_qtails(qtails, err)) return false;
+  memcpy(I->h_getq, &q, sizeof(DevGetQ));
+  HIP_CHECK(hipMemcpyAsync(I->d_gq, I->h_getq, sizeof(DevGetQ),
+                           hipMemcpyHostToDevice, I->stream));
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_get_find, dim3(1), dim3(256), 0, I->stream, I->A.run(),
+                     I->DA.run(), I->n, I->dn, I->spillA, I->d_qtails, I->d_gq,
+                     1, I->d_gtag, I->d_grev, I->d_gmeta);
+  HIP_CHECK(hipGetLastError());
+  uint64_t* h = I->h_ghdr;  // pinned scratch: tag | rev | meta | vo
+  HIP_CHECK(hipMemcpyAsync(h, I->d_gtag, 8, hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipMemcpyAsync(h + 1, I->d_grev, 8, hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipMemcpyAsync(h + 2, I->d_gmeta, 8, hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  const uint64_t tag = h[0];
+  const bool isd = (tag & ROW_TAG_DELTA) != 0;
+  const int64_t row = (int64_t)(tag & ROW_MASK);
+  if (tag == GET_ROW_NONE || row >= (isd ? I->dn : I->n) || h[1] != mod_rev ||
+      (h[2] & M_TOMB) || meta_vlen(h[2]) != vlen) {
+    if (err) *err = "get batch: a host-path query changed under the mutex";
+    return false;
+  }
+  HIP_CHECK(hipMemcpyAsync(h + 3, (isd ? I->DA.vo : I->A.vo) + row, 8,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  const uint64_t vo = h[3];
+  if (vo > (uint64_t)I->heap_used_ || vlen > (uint64_t)I->heap_used_ - vo) {
+    if (err) *err = "get batch: a host-path value lies outside the heap";
+    return false;
+  }
+  HIP_CHECK(hipEventRecord(I->ev_b1, I->stream));
+  HIP_CHECK(hipMemcpyAsync(dst, I->heapA + vo, vlen, hipMemcpyDeviceToHost,
+                           I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_b2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_b1, I->ev_b2);
+  perf.get_batch_d2h_ms += ms;
   return true;
 }
 

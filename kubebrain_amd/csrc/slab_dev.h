@@ -125,6 +125,12 @@ struct Perf {
   double list_ms = 0, list_d2h_ms = 0;
   int64_t list_batch_calls = 0, list_batch_q_dev = 0, list_batch_q_host = 0,
           list_batch_kvs = 0, list_batch_bytes = 0, list_emit_launches = 0;
+  // batched point read (kb_get_batch): k_get_find + k_get_plan + k_get_emit
+  // kernel time, the directory and value D2H, queries per path, entries with
+  // a kv, value bytes moved from the arena, three-kernel launches
+  double get_batch_ms = 0, get_batch_d2h_ms = 0;
+  int64_t get_batch_calls = 0, get_batch_q_dev = 0, get_batch_q_host = 0,
+          get_batch_found = 0, get_batch_bytes = 0, get_batch_launches = 0;
   // which mergeRuns branch ran (k_merge_small / k_merge_insert_inv /
   // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
   // async no-sync branch, and delta->base folds: the tests prove with these
@@ -161,6 +167,19 @@ constexpr uint32_t LS_MORE = 1;     // kb_list's `more` (found > limit)
 constexpr uint32_t LS_PARTIAL = 2;  // the winner table did not hold the whole
                                     // answer: the host path must serve it
 static_assert(sizeof(ListSize) == 16, "list size entry layout");
+// batched point read (kb_get_batch): what k_get_plan leaves per launch. The
+// entries are the reply's directory entries in wire form.
+struct GetDirEntry {
+  int32_t status, has_kv;
+  uint64_t header_rev, mod_rev, vlen;
+};
+struct GetBatchHdr {
+  uint64_t total;    // value bytes of the launch = extent of its arena layout
+  uint64_t skipped;  // queries k_get_emit did not copy (no bytes, or unsafe)
+  GetDirEntry dir[1];  // nq entries
+};
+static_assert(sizeof(GetDirEntry) == 32, "get directory entry layout");
+static_assert(sizeof(GetBatchHdr) == 48, "get launch header layout");
 
 
 
@@ -272,6 +291,26 @@ class Slab {
   bool GetBatchStart(const std::vector<DevGetQ>& qs, std::string* err,
                      const std::string& qtails = std::string());
   bool GetBatchFinish(int nq, std::vector<GetResult>* outs, std::string* err);
+  // batched point read with values (kb_get_batch).
+  // GetBatchLaunch uploads nq <= KB_MAX_Q queries and runs k_get_find,
+  // k_get_plan and (unless no_values) k_get_emit back to back, then reads
+  // back {total, skipped, nq directory entries}; *hdr points into pinned
+  // memory valid until the next call. The values of the launch lie packed in
+  // query order from arena offset 0, as far as the arena reaches.
+  bool GetBatchLaunch(const DevGetQ* qs, int nq, const std::string& qtails,
+                      bool no_values, uint64_t committed,
+                      const GetBatchHdr** hdr, std::string* err);
+  // arena [0, span) of the resident launch -> reply + reply_off, one D2H;
+  // reply is the pinned buffer of ListReply
+  bool GetBatchFetch(int64_t span, uint8_t* reply, int64_t reply_off,
+                     std::string* err);
+  // host path for one value the arena cannot hold: k_get_find for the query
+  // alone, then a plain D2H of its vlen heap bytes to dst. Fails if the row
+  // is not the (mod_rev, vlen) the batch's directory reported. Displaces the
+  // resident launch.
+  bool GetBatchHostValue(const DevGetQ& q, const std::string& qtails,
+                         uint64_t mod_rev, uint64_t vlen, uint8_t* dst,
+                         std::string* err);
 
   // compaction mark+sweep over encoded borders (compact.go:55-68 +
   // scanner.go:444-491, 566-591). Bounds are (key96, rev) pairs.

@@ -1484,6 +1484,158 @@ Status Store::ListBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
   return OK;
 }
 
+// Batched point read (kb_get_batch), per entry the result of
+// Get (range.go:34-121). Pass 1 runs every sub-batch of <= KB_MAX_Q queries
+// through k_get_find / k_get_plan / k_get_emit and keeps the finished
+// directory entries; the planner then lays out the reply, decides ENOBUF and
+// splits the values into emit rounds. Pass 2 moves each round's packed
+// values from the arena into the pinned reply: the first round of the
+// sub-batch whose launch is still resident straight away (the hot case: one
+// launch, two D2H copies), any other round after re-launching the kernels
+// over its queries alone — same mutex hold, same device state, so the
+// directory must come out the same. A value larger than the arena is copied
+// from the heap by the host.
+Status Store::GetBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                       size_t cap, size_t* out_len, uint64_t* total_found,
+                       std::string* errp) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  *out_len = 0;
+  if (total_found) *total_found = 0;
+  if ((flags & ~1) != 0 || n > 0x7fffffffull) return INVALID_ARG;
+  std::string errl;
+  std::string& err = errp ? *errp : errl;
+  if (!syncReads(&err)) return INTERNAL;
+  kbslab::Perf& perf = slab_->perf;
+  perf.get_batch_calls++;
+  const bool no_values = (flags & 1) != 0;
+  const uint64_t hdr = committed_;
+  const uint64_t arena = (uint64_t)slab_->arena_bytes();
+  const size_t max_q = (size_t)slab_->max_queries();
+  const size_t ngroups = (n + max_q - 1) / max_q;
+
+  // Get validates nothing about the key: every key is searched as it is
+  std::vector<DevGetQ> dq(n);
+  std::vector<std::string> tails(ngroups);
+  {
+    const uint8_t* p = qbuf;
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t klen;
+      uint64_t rev;
+      memcpy(&klen, p, 4); p += 4;
+      memcpy(&rev, p, 8); p += 8;
+      DevGetQ& q = dq[i];
+      memset(&q, 0, sizeof(q));
+      memcpy(q.key, p, std::min<size_t>(klen, (size_t)KEYW));
+      q.klen = klen;
+      if (klen > (uint32_t)KEYW) {
+        std::string& t = tails[i / max_q];
+        q.ko = t.size();
+        t.append((const char*)p + KEYW, klen - KEYW);
+      }
+      q.read_rev = rev == 0 ? UINT64_MAX : rev;  // as Store::get
+      p += klen;
+    }
+  }
+
+  // pass 1: directory entries of the whole call
+  std::vector<kbslab::GetDirEntry> dir(n);
+  std::vector<int32_t> has_kv(n);
+  std::vector<uint64_t> vlen(n);
+  int64_t resident = -1;      // sub-batch whose whole launch is in the arena
+  uint64_t res_skipped = 0;   // ... and what its emit skipped
+  for (size_t g = 0; g < ngroups; ++g) {
+    const size_t lo = g * max_q, cnt = std::min(max_q, n - lo);
+    const kbslab::GetBatchHdr* h = nullptr;
+    if (!slab_->GetBatchLaunch(&dq[lo], (int)cnt, tails[g], no_values, hdr, &h,
+                               &err))
+      return INTERNAL;
+    memcpy(&dir[lo], h->dir, cnt * sizeof(kbslab::GetDirEntry));
+    resident = (int64_t)g;
+    res_skipped = h->skipped;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    has_kv[i] = dir[i].has_kv;
+    vlen[i] = dir[i].vlen;
+  }
+
+  kbget::PlanOut plan;
+  int prc = kbget::Plan(has_kv.data(), vlen.data(), n, max_q, cap, arena, &plan);
+  if (prc != kbget::P_OK && prc != kbget::P_ENOBUF) {
+    err = "get batch: planner rejected the device directory";
+    return INTERNAL;
+  }
+  *out_len = (size_t)plan.required;
+  if (prc == kbget::P_ENOBUF) return NOBUF;  // the emit is discarded: no value D2H
+
+  // pass 2: values arrive round by round in the pinned reply; a reply
+  // without value bytes is written straight into the caller's buffer
+  const uint64_t dir_end = 4 + kbget::kDirEntry * (uint64_t)n;
+  uint8_t* reply = out;
+  if (plan.required > dir_end) {
+    reply = slab_->ListReply((int64_t)plan.required, &err);
+    if (!reply) return INTERNAL;
+  }
+  // The resident launch (the last sub-batch's) laid its values out from its
+  // first query: it holds a round iff no value byte precedes the round in
+  // that sub-batch. That round goes first, before a re-launch displaces it.
+  const size_t nrounds = plan.round_lo.size();
+  size_t first = nrounds;
+  for (size_t r = 0; r < nrounds && !no_values; ++r) {
+    const size_t lo = (size_t)plan.round_lo[r], g_lo = lo / max_q * max_q;
+    if (resident == (int64_t)(lo / max_q) && plan.val_off[lo] == plan.val_off[g_lo])
+      first = r;
+  }
+  std::vector<size_t> order;
+  if (first < nrounds) order.push_back(first);
+  for (size_t r = 0; r < nrounds; ++r)
+    if (r != first) order.push_back(r);
+  for (size_t r : order) {
+    const size_t lo = (size_t)plan.round_lo[r], hi = (size_t)plan.round_hi[r];
+    const size_t g = lo / max_q, g_lo = g * max_q;
+    const uint64_t span = plan.val_off[hi - 1] + vlen[hi - 1] - plan.val_off[lo];
+    size_t launched = 0, emits = 0;
+    uint64_t skipped = 0;
+    if (r == first) {
+      launched = std::min(max_q, n - g_lo);
+      skipped = res_skipped;
+    } else {
+      const kbslab::GetBatchHdr* h = nullptr;
+      if (!slab_->GetBatchLaunch(&dq[lo], (int)(hi - lo), tails[g], false, hdr,
+                                 &h, &err))
+        return INTERNAL;
+      if (memcmp(h->dir, &dir[lo], (hi - lo) * sizeof(kbslab::GetDirEntry)) != 0) {
+        err = "get batch: a re-launched round changed under the mutex";
+        return INTERNAL;
+      }
+      launched = hi - lo;
+      skipped = h->skipped;
+    }
+    for (size_t i = lo; i < hi; ++i) emits += plan.round[i] == (int32_t)r;
+    if (skipped != launched - emits) {
+      err = "get batch: the emit kernel skipped a value the plan placed";
+      return INTERNAL;
+    }
+    if (!slab_->GetBatchFetch((int64_t)span, reply, (int64_t)plan.val_off[lo],
+                              &err))
+      return INTERNAL;
+  }
+  for (size_t i = 0; i < n && plan.n_host > 0; ++i) {
+    if (plan.round[i] != kbget::R_HOST) continue;
+    if (!slab_->GetBatchHostValue(dq[i], tails[i / max_q], dir[i].mod_rev,
+                                  vlen[i], reply + plan.val_off[i], &err))
+      return INTERNAL;
+  }
+  const uint32_t n32 = (uint32_t)n;
+  memcpy(reply, &n32, 4);
+  if (n) memcpy(reply + 4, dir.data(), n * sizeof(kbslab::GetDirEntry));
+  if (reply != out) copyReply(out, reply, (size_t)plan.required);
+  perf.get_batch_q_host += (int64_t)plan.n_host;
+  perf.get_batch_q_dev += (int64_t)(n - plan.n_host);
+  perf.get_batch_found += (int64_t)plan.found;
+  if (total_found) *total_found = plan.found;
+  return OK;
+}
+
 CountResponse Store::Count(const Bytes& start, const Bytes& end, Status* st) {
   // range.go:177-205
   std::lock_guard<std::recursive_mutex> lk(mu_);
@@ -2077,9 +2229,26 @@ bool Store::BenchDel(const uint8_t* dbuf, size_t n, uint64_t* out_revs,
 
 std::string Store::PerfJson() {
   const kbslab::Perf& p = slab_->perf;
+  // Readers pass 4096-byte buffers, so the worst case has to stay below
+  // that, terminator included. The three formats below hold 171 + 166 + 558
+  // = 895 fixed characters and 62 conversions (7 + 7 + 29 = 43 integers,
+  // 2 + 2 + 15 = 19 floats). With every integer at 20 characters (sign + 19
+  // digits) and every float at 20 (a total below 1e15 ms with its decimals)
+  // the worst case is 895 + 62 * 20 = 2135 characters + 1 terminator: under
+  // 4096, and under this buffer, which therefore did not have to grow.
   char buf[3072];
   int at = snprintf(buf, sizeof(buf),
-           "{\"list_batch_calls\":%lld,\"list_batch_q_dev\":%lld,"
+           "{\"get_batch_calls\":%lld,\"get_batch_q_dev\":%lld,"
+           "\"get_batch_q_host\":%lld,\"get_batch_found\":%lld,"
+           "\"get_batch_bytes\":%lld,\"get_batch_launches\":%lld,"
+           "\"get_batch_ms\":%.3f,\"get_batch_d2h_ms\":%.3f,"
+           "\"get_launches\":%lld,",
+           (long long)p.get_batch_calls, (long long)p.get_batch_q_dev,
+           (long long)p.get_batch_q_host, (long long)p.get_batch_found,
+           (long long)p.get_batch_bytes, (long long)p.get_batch_launches,
+           p.get_batch_ms, p.get_batch_d2h_ms, (long long)p.get_launches);
+  at += snprintf(buf + at, sizeof(buf) - (size_t)at,
+           "\"list_batch_calls\":%lld,\"list_batch_q_dev\":%lld,"
            "\"list_batch_q_host\":%lld,\"list_batch_kvs\":%lld,"
            "\"list_batch_bytes\":%lld,\"list_emit_launches\":%lld,"
            "\"list_ms\":%.3f,\"list_d2h_ms\":%.3f,\"gather_launches\":%lld,",

@@ -18,6 +18,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "gplan.h"
 #include "lplan.h"
 #include "slab_dev.h"
 #include "wpoll.h"
@@ -78,6 +79,14 @@ class Store {
   Status ListBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
                    size_t cap, size_t* out_len, uint64_t* total_kvs,
                    std::string* err = nullptr);
+  // batched point read (kb_get_batch): n Gets under one mutex hold, the
+  // directory and the packed values written on the device;
+  // qbuf = n x {u32 klen; u64 rev; key}, reply = u32 n; n x {i32 status; i32
+  // has_kv; u64 header_rev; u64 mod_rev; u64 vlen}; then the values. flags
+  // bit 0 = no_values. NOBUF writes nothing (*out_len = required size).
+  Status GetBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                  size_t cap, size_t* out_len, uint64_t* total_found,
+                  std::string* err = nullptr);
   CountResponse Count(const Bytes& start, const Bytes& end, Status* st);
   uint64_t Compact(uint64_t revision, Status* st);
   uint64_t GetCurrentRevision();
