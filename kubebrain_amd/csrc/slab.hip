@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "slab_dev.h"
+#include "stepstage.h"
 
 namespace kbslab {
 
@@ -355,9 +356,14 @@ __global__ void k_range_bounds(Run b, int64_t n, Run d, int64_t dn,
                                const uint8_t* __restrict__ spill,
                                const uint8_t* __restrict__ qtails,
                                const DevRangeQ* __restrict__ qs, int nq,
-                               int64_t* __restrict__ bounds_g /*[4*nq]*/) {
+                               int64_t* __restrict__ bounds_g /*[4*nq]*/,
+                               unsigned long long* __restrict__ counters) {
   int q = blockIdx.x;
   if (q >= nq) return;
+  // rows-scanned / bytes-gathered of this batch start at 0: the scan and the
+  // gather that add to them follow this kernel in stream order, and the
+  // previous batch's read-back of them precedes it
+  if (q == 0 && threadIdx.x == 0) { counters[0] = 0; counters[1] = 0; }
   const DevRangeQ& Q = qs[q];
   const QKey qstart{Q.start, Q.start_klen, Q.start_ko, qtails};
   const QKey qend{Q.end, Q.end_klen, Q.end_ko, qtails};
@@ -1627,15 +1633,25 @@ struct Slab::Impl {
   uint8_t *spillA = nullptr, *spillB = nullptr;
   int64_t spill_cap = 0, spill_used_ = 0;
   // per-batch query-tail buffer (bounds/get keys > KEYW)
+  // d_qtails/d_qs/d_gq are what the kernels of the CURRENT batch read: the
+  // *_own buffers for a batch uploaded by the per-call entry points (every
+  // one of them passes through ensure_qtails first), slices of the step
+  // staging block for a staged bench step (StepStageCommit)
   uint8_t* d_qtails = nullptr;
+  uint8_t* d_qtails_own = nullptr;
   int64_t qt_cap = 0;
   bool ensure_qtails(const std::string& qt, std::string* err) {
     if ((int64_t)qt.size() > qt_cap) {
-      if (d_qtails) (void)hipFree(d_qtails);
+      if (d_qtails_own) (void)hipFree(d_qtails_own);
+      d_qtails_own = nullptr;
+      qt_cap = 0;
       int64_t cap = (int64_t)qt.size() * 2 + 4096;
-      HIP_CHECK(hipMalloc(&d_qtails, cap));
+      HIP_CHECK(hipMalloc(&d_qtails_own, cap));
       qt_cap = cap;
     }
+    d_qtails = d_qtails_own;
+    d_qs = d_qs_own;
+    d_gq = d_gq_own;
     if (!qt.empty())
       HIP_CHECK(hipMemcpyAsync(d_qtails, qt.data(), qt.size(),
                                hipMemcpyHostToDevice, stream));
@@ -1705,6 +1721,20 @@ struct Slab::Impl {
   int64_t arena_bytes = 384ll << 20;
   DevRangeQ* d_qs = nullptr;
   DevGetQ* d_gq = nullptr;
+  // step staging block (stepstage.h): ONE device allocation whose slices are
+  // the get queries, the range queries and their key tails, with a pinned
+  // double-buffered mirror the bench step fills in place, so a step uploads
+  // all three with one H2D. d_qs_own/d_gq_own are its max_q-sized slices,
+  // the targets of the per-call uploads.
+  uint8_t* d_stage = nullptr;
+  int64_t stage_cap = 0;
+  DevRangeQ* d_qs_own = nullptr;
+  DevGetQ* d_gq_own = nullptr;
+  uint8_t* h_stage[2] = {nullptr, nullptr};
+  hipEvent_t ev_stage[2] = {nullptr, nullptr};
+  int stage_idx = 0;
+  kbstage::StepLayout stage_lay;
+  int stage_nget = -1, stage_nrange = -1;  // -1: no step staged
   uint64_t* d_rows = nullptr;   // max_q*max_cap (base winners)
   uint64_t* d_rows2 = nullptr;  // delta winners
   uint64_t* d_rowsm = nullptr;  // merged winners
@@ -1714,8 +1744,15 @@ struct Slab::Impl {
   int32_t *d_ovf = nullptr, *d_found32 = nullptr;
   uint64_t *d_orev = nullptr, *d_ometa = nullptr;
   unsigned long long *d_scanned = nullptr, *d_bytes = nullptr;
-  uint8_t* h_resmeta = nullptr;  // pinned mirror of the resmeta block
+  // pinned mirrors of the resmeta block, one per batch slot: a batch's
+  // counters are read back by its own RangeBatchStart, so the next batch
+  // can be queued before the host looks at them (no stream drain)
+  uint8_t* h_resmeta[2] = {nullptr, nullptr};
   int64_t resmeta_bytes = 0;
+  // per-slot scan start / scan end / gather end / counters-on-host events
+  hipEvent_t ev_r0[2] = {nullptr, nullptr}, ev_r1[2] = {nullptr, nullptr},
+             ev_r2[2] = {nullptr, nullptr}, ev_rdy[2] = {nullptr, nullptr};
+  int rb_slot = 0;  // slot of the batch started last
   uint8_t* d_gbuf = nullptr;    // arena
   uint8_t* d_pack = nullptr;    // arena
   int64_t* d_goffs = nullptr;   // max_q+1
@@ -1853,8 +1890,17 @@ struct Slab::Impl {
 
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;  // async get lookup
-  uint64_t* h_gmeta = nullptr;   // pinned [2*max_q]: orev | ometa
-  int32_t* h_gfound = nullptr;   // pinned [max_q]
+  // d_orev | d_ometa | d_found32 are slices of one device block (d_orev is
+  // its base) with this pinned mirror: one D2H brings a lookup's results.
+  // The async lookup (launchGet) packs its three columns with stride nq at
+  // the block's start, so that copy is nq * 20 bytes.
+  uint8_t* h_getres = nullptr;
+  int64_t getres_bytes = 0;
+  // pinned double-buffered staging of EventRingPush (keys96 | revs)
+  uint8_t* h_evpush[2] = {nullptr, nullptr};
+  int64_t h_evpush_cap[2] = {0, 0};
+  hipEvent_t ev_evpush[2] = {nullptr, nullptr};
+  int evpush_idx = 0;
 
   // host staging (pinned for fast D2H)
   uint8_t* h_pack = nullptr;
@@ -1883,9 +1929,10 @@ struct Slab::Impl {
   Perf* perf = nullptr;           // -> Slab::perf (mergeRuns branch counters)
   bool validate_dn = false;       // KB_VALIDATE_DN: re-check async predictions
   // what the most recent RangeBatchFinish left behind (kb_test_last_range):
-  // its counters stay in h_resmeta, its records in d_gbuf and, for a
+  // its counters stay in h_resmeta[last_res], its records in d_gbuf and, for a
   // pipelined d2h batch, in h_packs[last_slot]
   int last_nq = 0;
+  int last_res = 0;  // its h_resmeta slot
   int64_t last_qcap = 0;
   bool last_pipe = false;
   int last_slot = 0;
@@ -1935,16 +1982,17 @@ struct Slab::Impl {
                     (void*)d_rows2, (void*)d_rowsm,
                     (void*)heapA, (void*)heapB, (void*)s_a, (void*)s_b,
                     (void*)s_c, (void*)s_d, (void*)s_e, (void*)lv1, (void*)lv1o, (void*)lv2,
-                    (void*)lv2o, (void*)lv3, (void*)lv3o, (void*)d_qs,
-                    (void*)d_gq, (void*)d_rows, (void*)d_offs,
+                    (void*)lv2o, (void*)lv3, (void*)lv3o,
+                    (void*)d_stage,  // holds d_qs_own and d_gq_own
+                    (void*)d_rows, (void*)d_offs,
                     (void*)d_found,  // base of the resmeta block
-                    (void*)d_found32, (void*)d_orev, (void*)d_ometa,
+                    (void*)d_orev,
                     (void*)shadow, (void*)d_outpos, (void*)d_mdup, (void*)d_mdupx,
                     (void*)d_mlbs, (void*)d_gbuf,
                     (void*)d_pack, (void*)d_goffs, (void*)d_bounds,
                     (void*)d_bkeys, (void*)d_brevs, (void*)d_dkeys,
                     (void*)d_dmeta, (void*)d_drev, (void*)d_dvo, (void*)d_dko,
-                    (void*)spillA, (void*)spillB, (void*)d_qtails,
+                    (void*)spillA, (void*)spillB, (void*)d_qtails_own,
                     (void*)A.ko, (void*)B.ko, (void*)DA.ko, (void*)DB.ko,
                     (void*)d_wpfx,
                     (void*)d_wplen, (void*)d_wlive, (void*)d_wfrom,
@@ -1955,7 +2003,14 @@ struct Slab::Impl {
     free_list();
     free_getb();
     if (h_pack) (void)hipHostFree(h_pack);
-    if (h_resmeta) (void)hipHostFree(h_resmeta);
+    for (int i = 0; i < 2; ++i) {
+      if (h_resmeta[i]) (void)hipHostFree(h_resmeta[i]);
+      if (h_stage[i]) (void)hipHostFree(h_stage[i]);
+      if (h_evpush[i]) (void)hipHostFree(h_evpush[i]);
+      for (hipEvent_t e : {ev_r0[i], ev_r1[i], ev_r2[i], ev_rdy[i], ev_stage[i],
+                           ev_evpush[i]})
+        if (e) (void)hipEventDestroy(e);
+    }
     for (int i = 0; i < 2; ++i) {
       if (h_uploads[i]) (void)hipHostFree(h_uploads[i]);
       if (ev_up[i]) (void)hipEventDestroy(ev_up[i]);
@@ -1964,8 +2019,7 @@ struct Slab::Impl {
       if (h_blob[i]) (void)hipHostFree(h_blob[i]);
       if (ev_blob[i]) (void)hipEventDestroy(ev_blob[i]);
     }
-    if (h_gmeta) (void)hipHostFree(h_gmeta);
-    if (h_gfound) (void)hipHostFree(h_gfound);
+    if (h_getres) (void)hipHostFree(h_getres);
     if (ev_g0) (void)hipEventDestroy(ev_g0);
     if (ev_g1) (void)hipEventDestroy(ev_g1);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -2208,8 +2262,6 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   HIP_CHECK_NULL(hipEventCreate(&I->ev3));
   HIP_CHECK_NULL(hipEventCreate(&I->ev_g0));
   HIP_CHECK_NULL(hipEventCreate(&I->ev_g1));
-  HIP_CHECK_NULL(hipHostMalloc(&I->h_gmeta, (int64_t)I->max_q * 16));
-  HIP_CHECK_NULL(hipHostMalloc(&I->h_gfound, (int64_t)I->max_q * 4));
   for (Impl::Col* c : {&I->A, &I->B}) {
     HIP_CHECK_NULL(hipMalloc(&c->keys, max_rows * KEYW));
     HIP_CHECK_NULL(hipMalloc(&c->meta, max_rows * 8));
@@ -2251,8 +2303,22 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   HIP_CHECK_NULL(hipMalloc(&I->lv2o, nb2 * 8));
   HIP_CHECK_NULL(hipMalloc(&I->lv3, 512 * 8));  // +256 spill slot for level 4
   HIP_CHECK_NULL(hipMalloc(&I->lv3o, 256 * 8));
-  HIP_CHECK_NULL(hipMalloc(&I->d_qs, sizeof(DevRangeQ) * I->max_q));
-  HIP_CHECK_NULL(hipMalloc(&I->d_gq, sizeof(DevGetQ) * I->max_q));
+  {
+    // step staging block: get queries | range queries | key tails
+    I->stage_cap = kbstage::StepCapacity(I->max_q, sizeof(DevGetQ),
+                                         sizeof(DevRangeQ),
+                                         env_i64("KB_STAGE_TAIL_BYTES", 256 << 10));
+    HIP_CHECK_NULL(hipMalloc(&I->d_stage, I->stage_cap));
+    I->d_gq_own = (DevGetQ*)I->d_stage;
+    I->d_qs_own = (DevRangeQ*)(I->d_stage +
+                               kbstage::align_up((int64_t)I->max_q * sizeof(DevGetQ)));
+    I->d_gq = I->d_gq_own;
+    I->d_qs = I->d_qs_own;
+    for (int i = 0; i < 2; ++i) {
+      HIP_CHECK_NULL(hipHostMalloc(&I->h_stage[i], I->stage_cap));
+      HIP_CHECK_NULL(hipEventCreate(&I->ev_stage[i]));
+    }
+  }
   HIP_CHECK_NULL(hipMalloc(&I->d_rows, (int64_t)I->max_q * I->max_cap * 8));
   HIP_CHECK_NULL(hipMalloc(&I->d_rows2, (int64_t)I->max_q * I->max_cap * 8));
   HIP_CHECK_NULL(hipMalloc(&I->d_rowsm, (int64_t)I->max_q * I->max_cap * 8));
@@ -2273,11 +2339,25 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
     I->d_ovf = (int32_t*)(base + I->max_q * 24);
     I->d_scanned = (unsigned long long*)(base + I->max_q * 24 + I->max_q * 4);
     I->d_bytes = I->d_scanned + 1;
-    HIP_CHECK_NULL(hipHostMalloc(&I->h_resmeta, I->resmeta_bytes));
+    for (int i = 0; i < 2; ++i) {
+      HIP_CHECK_NULL(hipHostMalloc(&I->h_resmeta[i], I->resmeta_bytes));
+      memset(I->h_resmeta[i], 0, I->resmeta_bytes);
+      HIP_CHECK_NULL(hipEventCreate(&I->ev_r0[i]));
+      HIP_CHECK_NULL(hipEventCreate(&I->ev_r1[i]));
+      HIP_CHECK_NULL(hipEventCreate(&I->ev_r2[i]));
+      HIP_CHECK_NULL(hipEventCreate(&I->ev_rdy[i]));
+    }
   }
-  HIP_CHECK_NULL(hipMalloc(&I->d_found32, I->max_q * 4));
-  HIP_CHECK_NULL(hipMalloc(&I->d_orev, I->max_q * 8));
-  HIP_CHECK_NULL(hipMalloc(&I->d_ometa, I->max_q * 8));
+  {
+    // orev | ometa | found32 of a point lookup: one block, one pinned mirror
+    uint8_t* base = nullptr;
+    I->getres_bytes = (int64_t)I->max_q * 20;
+    HIP_CHECK_NULL(hipMalloc(&base, I->getres_bytes));
+    I->d_orev = (uint64_t*)base;
+    I->d_ometa = I->d_orev + I->max_q;
+    I->d_found32 = (int32_t*)(I->d_ometa + I->max_q);
+    HIP_CHECK_NULL(hipHostMalloc(&I->h_getres, I->getres_bytes));
+  }
   HIP_CHECK_NULL(hipMalloc(&I->d_gbuf, I->arena_bytes));
   HIP_CHECK_NULL(hipMalloc(&I->d_pack, I->arena_bytes));
   HIP_CHECK_NULL(hipMalloc(&I->d_goffs, (I->max_q + 1) * 8));
@@ -2308,8 +2388,6 @@ bool Slab::SpillAppend(const void* src, int64_t len, int64_t* off,
   if (len > (8 << 20)) {
     HIP_CHECK(hipMemcpyAsync(I->spillA + I->spill_used_, src, len,
                              hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->spillB + I->spill_used_, src, len,
-                             hipMemcpyHostToDevice, I->stream));
     HIP_CHECK(hipStreamSynchronize(I->stream));
     *off = I->spill_used_;
     I->spill_used_ += len;
@@ -2319,14 +2397,16 @@ bool Slab::SpillAppend(const void* src, int64_t len, int64_t* off,
   if (!h) return false;
   HIP_CHECK(hipMemcpyAsync(I->spillA + I->spill_used_, h, len,
                            hipMemcpyHostToDevice, I->stream));
-  HIP_CHECK(hipMemcpyAsync(I->spillB + I->spill_used_, h, len,
-                           hipMemcpyHostToDevice, I->stream));
   HIP_CHECK(hipEventRecord(I->ev_blob[I->blob_idx], I->stream));
   *off = I->spill_used_;
   I->spill_used_ += len;
   return true;
 }
 
+// Appends go to heapA/spillA only. heapB/spillB are Compact's destination:
+// k_heap_scatter/k_spill_scatter write every surviving record into them from
+// the A side and nothing reads them before that, so mirroring each append
+// into them only doubled the bytes crossing the host link.
 bool Slab::HeapAppend(const void* src, int64_t len, int64_t* off, std::string* err) {
   Impl* I = p;
   if (len == 0) { *off = I->heap_used_; return true; }
@@ -2337,8 +2417,6 @@ bool Slab::HeapAppend(const void* src, int64_t len, int64_t* off, std::string* e
   if (len > (8 << 20)) {  // bulk loads: pageable copy + sync beats GB-scale pinned staging
     HIP_CHECK(hipMemcpyAsync(I->heapA + I->heap_used_, src, len,
                              hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->heapB + I->heap_used_, src, len,
-                             hipMemcpyHostToDevice, I->stream));
     HIP_CHECK(hipStreamSynchronize(I->stream));
     *off = I->heap_used_;
     I->heap_used_ += len;
@@ -2347,8 +2425,6 @@ bool Slab::HeapAppend(const void* src, int64_t len, int64_t* off, std::string* e
   uint8_t* h = I->stage_blob(src, len, err);
   if (!h) return false;
   HIP_CHECK(hipMemcpyAsync(I->heapA + I->heap_used_, h, len,
-                           hipMemcpyHostToDevice, I->stream));
-  HIP_CHECK(hipMemcpyAsync(I->heapB + I->heap_used_, h, len,
                            hipMemcpyHostToDevice, I->stream));
   HIP_CHECK(hipEventRecord(I->ev_blob[I->blob_idx], I->stream));
   *off = I->heap_used_;
@@ -2360,41 +2436,68 @@ bool Slab::AppendRows(const uint8_t* keys, const uint64_t* meta,
                       const uint64_t* rev, const uint64_t* vo,
                       const uint64_t* ko, int64_t m,
                       std::string* err, int64_t known_new_dn) {
+  if (m == 0) return true;
+  RowUpload u;
+  if (!BeginRowUpload(m, &u, err)) return false;
+  memcpy(u.keys, keys, m * KEYW);
+  memcpy(u.meta, meta, m * 8);
+  memcpy(u.rev, rev, m * 8);
+  memcpy(u.vo, vo, m * 8);
+  memcpy(u.ko, ko, m * 8);
+  return CommitRowUpload(m, err, known_new_dn);
+}
+
+bool Slab::BeginRowUpload(int64_t m, RowUpload* u, std::string* err) {
+  Impl* I = p;
+  kbstage::RowLayout l;
+  if (m > I->delta_cap) { if (err) *err = "append larger than delta cap"; return false; }
+  if (!I->ensure_delta(m, err)) return false;
+  if (!kbstage::PlanRows(m, I->upload_cap, KEYW, &l)) {
+    if (err) *err = "row upload: bad row count";
+    return false;
+  }
+  // double-buffered pinned mirror: wait only for THIS slot's previous
+  // upload (two steps back — long since done), never the whole stream
+  int slot = I->up_idx ^= 1;
+  HIP_CHECK(hipEventSynchronize(I->ev_up[slot]));
+  uint8_t* h = I->h_uploads[slot];
+  u->keys = h + l.off_keys;
+  u->meta = (uint64_t*)(h + l.off_meta);
+  u->rev = (uint64_t*)(h + l.off_rev);
+  u->vo = (uint64_t*)(h + l.off_vo);
+  u->ko = (uint64_t*)(h + l.off_ko);
+  return true;
+}
+
+bool Slab::CommitRowUpload(int64_t m, std::string* err, int64_t known_new_dn) {
   Impl* I = p;
   if (m == 0) return true;
+  kbstage::RowLayout l;
+  if (!kbstage::PlanRows(m, I->upload_cap, KEYW, &l)) {
+    if (err) *err = "row upload: commit without begin";
+    return false;
+  }
   if (I->dn + m > I->delta_cap) {
     // fold first to make room (prediction no longer valid: go sync)
     if (!Fold(err)) return false;
     known_new_dn = -1;
-    if (m > I->delta_cap) { if (err) *err = "append larger than delta cap"; return false; }
   }
   bool async = known_new_dn >= 0 && !I->validate_dn;
   if (!async) HIP_CHECK(hipEventRecord(I->ev0, I->stream));
-  if (!I->ensure_delta(m, err)) return false;
   {
-    // double-buffered pinned mirror: wait only for THIS slot's previous
-    // upload (two steps back — long since done), never the whole stream
-    int slot = I->up_idx ^= 1;
-    HIP_CHECK(hipEventSynchronize(I->ev_up[slot]));
-    int64_t cap = I->upload_cap;
-    uint8_t* h = I->h_uploads[slot];
-    memcpy(h, keys, m * KEYW);
-    memcpy(h + cap * KEYW, meta, m * 8);
-    memcpy(h + cap * KEYW + cap * 8, rev, m * 8);
-    memcpy(h + cap * KEYW + cap * 16, vo, m * 8);
-    memcpy(h + cap * KEYW + cap * 24, ko, m * 8);
-    // pinned source => truly async enqueues (no staging-pool stall)
-    HIP_CHECK(hipMemcpyAsync(I->d_dkeys, h, m * KEYW, hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->d_dmeta, h + cap * KEYW, m * 8, hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->d_drev, h + cap * KEYW + cap * 8, m * 8, hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->d_dvo, h + cap * KEYW + cap * 16, m * 8, hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->d_dko, h + cap * KEYW + cap * 24, m * 8, hipMemcpyHostToDevice, I->stream));
+    // the columns lie with stride m in the mirror and in the device block:
+    // one contiguous span, ONE H2D; pinned source => a truly async enqueue
+    int slot = I->up_idx;
+    HIP_CHECK(hipMemcpyAsync(I->d_dkeys, I->h_uploads[slot], l.total,
+                             hipMemcpyHostToDevice, I->stream));
     HIP_CHECK(hipEventRecord(I->ev_up[slot], I->stream));
   }
   int64_t new_dn = async ? known_new_dn : 0;  // async: mergeRuns reads it
   if (kb_trace()) fprintf(stderr, "[trace] AppendRows n=%lld m=%lld async=%d\n",
                           (long long)I->dn, (long long)m, (int)async);
-  Run up{I->d_dkeys, I->d_dmeta, I->d_drev, I->d_dvo, I->d_dko};
+  Run up{I->d_dkeys, (uint64_t*)(I->d_dkeys + l.off_meta),
+         (uint64_t*)(I->d_dkeys + l.off_rev), (uint64_t*)(I->d_dkeys + l.off_vo),
+         (uint64_t*)(I->d_dkeys + l.off_ko)};
   // shadow-mark the base rows of every inserted key BEFORE the merge
   // kernels queue (same stream => ordering is irrelevant, both read only
   // the base run and the upload)
@@ -2406,9 +2509,7 @@ bool Slab::AppendRows(const uint8_t* keys, const uint64_t* meta,
                     /*device_newn_ok=*/async))
     return false;
   if (async) {
-    // kernels queue on the stream; subsequent reads queue behind them.
-    // NOTE: the host `keys/meta/rev/vo` buffers were consumed by the H2D
-    // copies above, which HIP stages synchronously for pageable memory.
+    // kernels queue on the stream; subsequent reads queue behind them
     perf.merges++;
     perf.merges_async++;
     std::swap(I->DA, I->DB);
@@ -2468,8 +2569,6 @@ bool Slab::Merge(const DeltaRows& d, std::string* err) {
   if (!d.heap.empty()) {
     HIP_CHECK(hipMemcpyAsync(I->heapA + I->heap_used_, d.heap.data(),
                              d.heap.size(), hipMemcpyHostToDevice, I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->heapB + I->heap_used_, d.heap.data(),
-                             d.heap.size(), hipMemcpyHostToDevice, I->stream));
     I->heap_used_ += (int64_t)d.heap.size();
   }
   if (d.m > 0) {
@@ -2520,6 +2619,7 @@ bool Slab::RangeScanStart(const std::vector<DevRangeQ>& qs, std::string* err,
   if (nq == 0) return true;
   if (nq > I->max_q) { if (err) *err = "too many queries per batch (KB_MAX_Q)"; return false; }
   if (!I->ensure_qtails(qtails, err)) return false;
+  I->stage_nrange = -1;  // the staging block no longer holds the current batch
   {
     // pinned double-buffered query upload (a 900-query batch is ~200 KB;
     // pageable hipMemcpyAsync stalls the host on the staging pool)
@@ -2536,28 +2636,45 @@ bool Slab::RangeScanStart(const std::vector<DevRangeQ>& qs, std::string* err,
                              hipMemcpyHostToDevice, I->stream));
     HIP_CHECK(hipEventRecord(I->ev_qs[slot], I->stream));
   }
-  HIP_CHECK(hipMemsetAsync(I->d_scanned, 0, 8, I->stream));
-  HIP_CHECK(hipMemsetAsync(I->d_bytes, 0, 8, I->stream));
-  HIP_CHECK(hipEventRecord(I->ev0, I->stream));
+  return launchScan(nq, err);
+}
+
+// scan half over the current batch's queries (I->d_qs / I->d_qtails, already
+// queued for upload): takes the next batch slot and records its scan events
+bool Slab::launchScan(int nq, std::string* err) {
+  Impl* I = p;
+  const int rs = I->rb_slot ^= 1;
+  HIP_CHECK(hipEventRecord(I->ev_r0[rs], I->stream));
+  static_assert(sizeof(unsigned long long) == 8, "counter pair layout");
   hipLaunchKernelGGL(k_range_bounds, dim3(nq), dim3(256), 0, I->stream,
                      I->A.run(), I->n, I->DA.run(), I->dn, I->spillA,
-                     I->d_qtails, I->d_qs, nq, I->d_bounds4);
+                     I->d_qtails, I->d_qs, nq, I->d_bounds4,
+                     I->d_scanned /* d_bytes == d_scanned + 1 */);
   hipLaunchKernelGGL(k_range_scan2, dim3(nq), dim3((uint32_t)I->scan_t), 0, I->stream,
                      I->A.run(), I->n, I->DA.run(), I->dn, I->spillA,
                      I->d_qtails, I->d_qs, nq,
                      I->max_cap, I->d_rows, I->d_rows2, I->d_rowsm, I->d_found,
                      I->d_total, I->d_scanned, I->d_bounds4, I->shadow,
                      I->d_dbg);
-  HIP_CHECK(hipEventRecord(I->ev1, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_r1[rs], I->stream));
   return true;
 }
 
 bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
                            const std::string& qtails) {
-  Impl* I = p;
   int nq = (int)qs.size();
   if (!RangeScanStart(qs, err, qtails)) return false;
   if (nq == 0) return true;
+  return launchGather(qs.data(), nq, err);
+}
+
+int Slab::range_slot() const { return p->rb_slot; }
+
+// gather half + the batch's counter read-back into its slot's pinned mirror.
+// hq = the batch's queries in host memory (their caps size gather mode 2).
+bool Slab::launchGather(const DevRangeQ* hq, int nq, std::string* err) {
+  Impl* I = p;
+  const int rs = I->rb_slot;
   int64_t qcap = I->arena_bytes / nq;
   qcap &= ~15ll;
   hipLaunchKernelGGL(k_gather, dim3(nq), dim3(256), 0, I->stream, I->A.run(),
@@ -2566,8 +2683,9 @@ bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
                      I->d_gbytes, I->d_ovf, I->d_bytes);
   if (I->gather_mode == 2) {
     int64_t maxw = 0;
-    for (const DevRangeQ& q : qs) {
-      int64_t c = q.cap > 0 && q.cap < I->max_cap ? q.cap : I->max_cap;
+    for (int i = 0; i < nq; ++i) {
+      int64_t qc = hq[i].cap;  // packed struct: copy, do not bind
+      int64_t c = qc > 0 && qc < I->max_cap ? qc : I->max_cap;
       if (c > maxw) maxw = c;
     }
     hipLaunchKernelGGL(k_gather_copy2,
@@ -2581,7 +2699,13 @@ bool Slab::RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
                        I->max_cap, I->d_found, I->d_qs, nq, I->d_gbuf, qcap,
                        I->d_offs, I->d_ovf, I->gather_gwl);
   }
-  HIP_CHECK(hipEventRecord(I->ev2, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_r2[rs], I->stream));
+  // found/total/gbytes/ovf/scanned/bytes share one device block: one D2H
+  // into this slot's pinned mirror. RangeBatchFinish waits on ev_rdy of the
+  // slot alone, so a later batch may already be queued behind this one.
+  HIP_CHECK(hipMemcpyAsync(I->h_resmeta[rs], I->d_found, I->resmeta_bytes,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_rdy[rs], I->stream));
   return true;
 }
 
@@ -2593,56 +2717,42 @@ bool Slab::RangeBatchEx(const std::vector<DevRangeQ>& qs, bool d2h, bool parse,
 }
 
 bool Slab::RangeBatchFinish(int nq, bool d2h, bool parse,
-                            std::vector<RangeResult>* outs, std::string* err) {
+                            std::vector<RangeResult>* outs, std::string* err,
+                            int slot) {
   Impl* I = p;
   outs->assign(nq, RangeResult());
   if (nq == 0) return true;
+  const int rs = slot >= 0 ? (slot & 1) : I->rb_slot;
+  if (d2h && rs != I->rb_slot) {
+    if (err) *err = "range finish: d2h of a batch that is no longer the latest";
+    return false;
+  }
   int64_t qcap = I->arena_bytes / nq;
   qcap &= ~15ll;
   I->last_nq = nq;
   I->last_qcap = qcap;
   I->last_pipe = d2h && !parse;
-  // small result metadata: d_found/d_total/d_gbytes are CONTIGUOUS slices of
-  // one allocation (see Create), so one D2H covers them; ovf+counters ride
-  // two more copies
-  // found/total/gbytes/ovf/scanned/bytes share one device block: one D2H
-  // into the pinned mirror instead of six small copies on the store stream
+  I->last_res = rs;
+  // the counters were read back by the batch's own start; wait for THAT
+  // copy only (never the stream: a later batch may be queued behind it)
   std::vector<int64_t> found(nq), total(nq), gbytes(nq);
   std::vector<int32_t> ovf(nq);
   unsigned long long scanned = 0, bytes = 0;
   {
-    if (kb_trace()) {
-      fprintf(stderr, "[trace] RBFinish nq=%d readback %lld B h=%p d=%p\n", nq, (long long)I->resmeta_bytes, (void*)I->h_resmeta, (void*)I->d_found);
-      hipPointerAttribute_t pa{};
-      hipError_t pe = hipPointerGetAttributes(&pa, I->d_found);
-      fprintf(stderr, "[trace] dev attr rc=%d type=%d\n", (int)pe, (int)pa.type);
-      pe = hipPointerGetAttributes(&pa, I->h_resmeta);
-      fprintf(stderr, "[trace] host attr rc=%d type=%d\n", (int)pe, (int)pa.type);
-    }
-    if (env_i64("KB_SYNC_READBACK", 0)) {
-      HIP_CHECK(hipStreamSynchronize(I->stream));
-      if (kb_trace()) fprintf(stderr, "[trace] f0 pre-synced\n");
-      HIP_CHECK(hipMemcpy(I->h_resmeta, I->d_found, I->resmeta_bytes,
-                          hipMemcpyDeviceToHost));
-    } else {
-      HIP_CHECK(hipMemcpyAsync(I->h_resmeta, I->d_found, I->resmeta_bytes,
-                               hipMemcpyDeviceToHost, I->stream));
-      if (kb_trace()) fprintf(stderr, "[trace] f1 copy enq\n");
-      HIP_CHECK(hipStreamSynchronize(I->stream));
-    }
-    if (kb_trace()) fprintf(stderr, "[trace] f2 synced\n");
-    memcpy(found.data(), I->h_resmeta, nq * 8);
-    memcpy(total.data(), I->h_resmeta + I->max_q * 8, nq * 8);
-    memcpy(gbytes.data(), I->h_resmeta + I->max_q * 16, nq * 8);
-    memcpy(ovf.data(), I->h_resmeta + I->max_q * 24, nq * 4);
-    memcpy(&scanned, I->h_resmeta + I->max_q * 28, 8);
-    memcpy(&bytes, I->h_resmeta + I->max_q * 28 + 8, 8);
-    if (kb_trace()) fprintf(stderr, "[trace] f3 memcpys done w0=%lld ovf0=%d\n", (long long)found[0], (int)ovf[0]);
+    HIP_CHECK(hipEventSynchronize(I->ev_rdy[rs]));
+    const uint8_t* hm = I->h_resmeta[rs];
+    memcpy(found.data(), hm, nq * 8);
+    memcpy(total.data(), hm + I->max_q * 8, nq * 8);
+    memcpy(gbytes.data(), hm + I->max_q * 16, nq * 8);
+    memcpy(ovf.data(), hm + I->max_q * 24, nq * 4);
+    memcpy(&scanned, hm + I->max_q * 28, 8);
+    memcpy(&bytes, hm + I->max_q * 28 + 8, 8);
+    if (kb_trace()) fprintf(stderr, "[trace] RBFinish nq=%d slot=%d w0=%lld ovf0=%d\n", nq, rs, (long long)found[0], (int)ovf[0]);
   }
   float ms = 0;
-  (void)hipEventElapsedTime(&ms, I->ev0, I->ev1);
+  (void)hipEventElapsedTime(&ms, I->ev_r0[rs], I->ev_r1[rs]);
   perf.scan_ms += ms;
-  (void)hipEventElapsedTime(&ms, I->ev1, I->ev2);
+  (void)hipEventElapsedTime(&ms, I->ev_r1[rs], I->ev_r2[rs]);
   perf.gather_ms += ms;
   if (I->d_dbg) {  // KB_SCAN_DBG: block-serial ms per phase, summed over blocks
     unsigned long long c[8] = {0};
@@ -2776,7 +2886,7 @@ bool Slab::LastRangeWire(int src, std::string* wire, std::string* err) {
   }
   if (!DrainD2H(err)) return false;
   HIP_CHECK(hipStreamSynchronize(I->stream));
-  const uint8_t* hm = I->h_resmeta;
+  const uint8_t* hm = I->h_resmeta[I->last_res];
   std::vector<int64_t> found(nq), total(nq), gbytes(nq), goffs(nq + 1);
   std::vector<int32_t> ovf(nq);
   if (nq > 0) {
@@ -2860,7 +2970,7 @@ bool Slab::ListSizeBatch(const std::vector<DevRangeQ>& qs,
                            I->d_scanned, 8, hipMemcpyDeviceToHost, I->stream));
   HIP_CHECK(hipStreamSynchronize(I->stream));
   float ms = 0;
-  (void)hipEventElapsedTime(&ms, I->ev0, I->ev1);
+  (void)hipEventElapsedTime(&ms, I->ev_r0[I->rb_slot], I->ev_r1[I->rb_slot]);
   perf.scan_ms += ms;
   ms = 0;
   (void)hipEventElapsedTime(&ms, I->ev_l0, I->ev_l1);
@@ -3075,20 +3185,97 @@ bool Slab::GetBatchStart(const std::vector<DevGetQ>& qs, std::string* err,
   if (nq == 0) return true;
   if (nq > I->max_q) { if (err) *err = "too many gets per batch"; return false; }
   if (!I->ensure_qtails(qtails, err)) return false;
+  I->stage_nget = -1;  // the staging block no longer holds the current batch
   HIP_CHECK(hipMemcpyAsync(I->d_gq, qs.data(), sizeof(DevGetQ) * nq,
                            hipMemcpyHostToDevice, I->stream));
+  return launchGet(nq, err);
+}
+
+// meta-only lookup over the current batch's get queries (I->d_gq /
+// I->d_qtails) + ONE D2H of the orev|ometa|found32 block
+bool Slab::launchGet(int nq, std::string* err) {
+  Impl* I = p;
   HIP_CHECK(hipEventRecord(I->ev_g0, I->stream));
   int blocks = (int)ceil_div(nq, 4);
   hipLaunchKernelGGL(k_get2, dim3(blocks), dim3(256), 0, I->stream,
                      I->A.run(), I->DA.run(), I->n, I->dn, I->spillA,
                      I->d_qtails, I->heapA, I->d_gq, nq, 0,
-                     I->d_gbuf, 0, I->d_orev, I->d_ometa, I->d_found32,
-                     I->d_ovf);
-  HIP_CHECK(hipMemcpyAsync(I->h_gmeta, I->d_orev, nq * 8, hipMemcpyDeviceToHost, I->stream));
-  HIP_CHECK(hipMemcpyAsync(I->h_gmeta + I->max_q, I->d_ometa, nq * 8, hipMemcpyDeviceToHost, I->stream));
-  HIP_CHECK(hipMemcpyAsync(I->h_gfound, I->d_found32, nq * 4, hipMemcpyDeviceToHost, I->stream));
+                     I->d_gbuf, 0, I->d_orev, I->d_orev + nq,
+                     (int32_t*)(I->d_orev + 2 * nq), I->d_ovf);
+  // the three result columns lie with stride nq in the block (GetBatchFinish
+  // reads them so): the read-back is the nq * 20 bytes of this lookup
+  HIP_CHECK(hipMemcpyAsync(I->h_getres, I->d_orev, (int64_t)nq * 20,
+                           hipMemcpyDeviceToHost, I->stream));
   HIP_CHECK(hipEventRecord(I->ev_g1, I->stream));
   return true;
+}
+
+// ---- step staging block (bench step: one upload for gets, ranges, tails) --
+
+bool Slab::StepStageBegin(int nget, int nrange, StepStage* st, std::string* err) {
+  Impl* I = p;
+  I->stage_nget = I->stage_nrange = -1;
+  kbstage::StepLayout l;
+  if (!kbstage::PlanStep(nget, nrange, I->max_q, sizeof(DevGetQ),
+                         sizeof(DevRangeQ), I->stage_cap, &l)) {
+    if (err) *err = "too many queries per batch (KB_MAX_Q)";
+    return false;
+  }
+  // wait only for this slot's previous upload (two steps back)
+  int slot = I->stage_idx ^= 1;
+  HIP_CHECK(hipEventSynchronize(I->ev_stage[slot]));
+  I->stage_lay = l;
+  uint8_t* h = I->h_stage[slot];
+  st->gq = (DevGetQ*)(h + l.off_getq);
+  st->rq = (DevRangeQ*)(h + l.off_rangeq);
+  st->tails = h + l.off_tails;
+  st->tail_cap = l.tail_cap;
+  I->stage_nget = nget;
+  I->stage_nrange = nrange;
+  return true;
+}
+
+bool Slab::StepStageCommit(int64_t tail_bytes, std::string* err) {
+  Impl* I = p;
+  if (I->stage_nget < 0 || I->stage_nrange < 0) {
+    if (err) *err = "step stage: commit without begin";
+    return false;
+  }
+  const kbstage::StepLayout& l = I->stage_lay;
+  int64_t span = kbstage::StepSpan(l, tail_bytes);
+  if (span < 0) {
+    I->stage_nget = I->stage_nrange = -1;
+    if (err) *err = "step stage: key tails exceed the staging block";
+    return false;
+  }
+  int slot = I->stage_idx;
+  if (span > 0) {
+    HIP_CHECK(hipMemcpyAsync(I->d_stage, I->h_stage[slot], span,
+                             hipMemcpyHostToDevice, I->stream));
+    HIP_CHECK(hipEventRecord(I->ev_stage[slot], I->stream));
+  }
+  // the kernels of this step read the staged slices
+  I->d_gq = (DevGetQ*)(I->d_stage + l.off_getq);
+  I->d_qs = (DevRangeQ*)(I->d_stage + l.off_rangeq);
+  I->d_qtails = I->d_stage + l.off_tails;
+  return true;
+}
+
+bool Slab::GetBatchStartStaged(std::string* err) {
+  Impl* I = p;
+  if (I->stage_nget < 0) { if (err) *err = "step stage: no staged gets"; return false; }
+  if (I->stage_nget == 0) return true;
+  return launchGet(I->stage_nget, err);
+}
+
+bool Slab::RangeBatchStartStaged(std::string* err) {
+  Impl* I = p;
+  if (I->stage_nrange < 0) { if (err) *err = "step stage: no staged ranges"; return false; }
+  int nq = I->stage_nrange;
+  if (nq == 0) return true;
+  if (!launchScan(nq, err)) return false;
+  return launchGather((const DevRangeQ*)(I->h_stage[I->stage_idx] +
+                                         I->stage_lay.off_rangeq), nq, err);
 }
 
 bool Slab::GetBatchFinish(int nq, std::vector<GetResult>* outs, std::string* err) {
@@ -3100,12 +3287,15 @@ bool Slab::GetBatchFinish(int nq, std::vector<GetResult>* outs, std::string* err
   (void)hipEventElapsedTime(&ms, I->ev_g0, I->ev_g1);
   perf.get_ms += ms;
   perf.get_launches++;
+  const uint64_t* h_orev = (const uint64_t*)I->h_getres;
+  const uint64_t* h_ometa = h_orev + nq;
+  const int32_t* h_found = (const int32_t*)(h_ometa + nq);
   for (int q = 0; q < nq; ++q) {
     GetResult& g = (*outs)[q];
-    g.found = I->h_gfound[q] != 0;
+    g.found = h_found[q] != 0;
     if (!g.found) continue;
-    uint64_t m = I->h_gmeta[I->max_q + q];
-    g.rev = I->h_gmeta[q];
+    uint64_t m = h_ometa[q];
+    g.rev = h_orev[q];
     g.tomb = (m & M_TOMB) != 0;
     g.vlen = meta_vlen(m);
   }
@@ -3357,20 +3547,43 @@ bool Slab::EventRingPush(const uint8_t* keys96, const uint64_t* revs,
   Impl* I = p;
   if (!I->er_keys) { if (err) *err = "event ring not initialized"; return false; }
   // contiguous seqs; the ring may wrap once per push
+  if (count <= 0) return true;
+  if (count > I->er_cap) { if (err) *err = "event push larger than the ring"; return false; }
   int64_t s0 = base_seq % I->er_cap;
   int64_t first = std::min(count, I->er_cap - s0);
-  HIP_CHECK(hipMemcpyAsync(I->er_keys + s0 * KEYW, keys96, first * KEYW,
+  // stage keys|revs in a pinned double-buffered block (the callers' vectors
+  // are pageable and die on return) and queue the copies without draining
+  // the stream: WatchFilterRing, WatchCatchup and the payload ring queue on
+  // the same stream, so they see the pushed span. Slot reuse waits on that
+  // slot's own copies only.
+  int slot = I->evpush_idx ^= 1;
+  if (!I->ev_evpush[slot]) HIP_CHECK(hipEventCreate(&I->ev_evpush[slot]));
+  HIP_CHECK(hipEventSynchronize(I->ev_evpush[slot]));
+  int64_t need = count * (KEYW + 8);
+  if (need > I->h_evpush_cap[slot]) {
+    if (I->h_evpush[slot]) (void)hipHostFree(I->h_evpush[slot]);
+    I->h_evpush[slot] = nullptr;
+    I->h_evpush_cap[slot] = 0;
+    int64_t cap = std::max<int64_t>(need, 512 * (KEYW + 8));
+    HIP_CHECK(hipHostMalloc(&I->h_evpush[slot], cap));
+    I->h_evpush_cap[slot] = cap;
+  }
+  uint8_t* hk = I->h_evpush[slot];
+  uint64_t* hr = (uint64_t*)(hk + count * KEYW);
+  memcpy(hk, keys96, count * KEYW);
+  memcpy(hr, revs, count * 8);
+  HIP_CHECK(hipMemcpyAsync(I->er_keys + s0 * KEYW, hk, first * KEYW,
                            hipMemcpyHostToDevice, I->stream));
-  HIP_CHECK(hipMemcpyAsync(I->er_rev + s0, revs, first * 8,
+  HIP_CHECK(hipMemcpyAsync(I->er_rev + s0, hr, first * 8,
                            hipMemcpyHostToDevice, I->stream));
   if (first < count) {
-    HIP_CHECK(hipMemcpyAsync(I->er_keys, keys96 + first * KEYW,
+    HIP_CHECK(hipMemcpyAsync(I->er_keys, hk + first * KEYW,
                              (count - first) * KEYW, hipMemcpyHostToDevice,
                              I->stream));
-    HIP_CHECK(hipMemcpyAsync(I->er_rev, revs + first, (count - first) * 8,
+    HIP_CHECK(hipMemcpyAsync(I->er_rev, hr + first, (count - first) * 8,
                              hipMemcpyHostToDevice, I->stream));
   }
-  HIP_CHECK(hipStreamSynchronize(I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_evpush[slot], I->stream));
   return true;
 }
 

@@ -70,6 +70,9 @@ struct DevGetQ {
   uint64_t read_rev;  // UINT64_MAX for "latest"
 };
 #pragma pack(pop)
+// the step staging block's layout (stepstage.h) is checked at these sizes
+static_assert(sizeof(DevRangeQ) == 248 && sizeof(DevGetQ) == 120,
+              "device query layout");
 
 struct RangeResult {
   int64_t written = 0;   // winners materialized (<= cap)
@@ -217,6 +220,13 @@ class Slab {
   bool AppendRows(const uint8_t* keys, const uint64_t* meta, const uint64_t* rev,
                   const uint64_t* vo, const uint64_t* ko, int64_t m,
                   std::string* err, int64_t known_new_dn = -1);
+  // the same without the intermediate vectors: BeginRowUpload hands out the
+  // five column slices of a pinned mirror (stride m, stepstage.h PlanRows),
+  // the caller writes its m sorted rows into them, CommitRowUpload queues
+  // ONE H2D of the span and the merge. AppendRows is Begin + memcpy + Commit.
+  struct RowUpload { uint8_t* keys; uint64_t *meta, *rev, *vo, *ko; };
+  bool BeginRowUpload(int64_t m, RowUpload* u, std::string* err);
+  bool CommitRowUpload(int64_t m, std::string* err, int64_t known_new_dn = -1);
   // fold the delta run into the base run; delta becomes empty
   bool Fold(std::string* err);
 
@@ -238,9 +248,30 @@ class Slab {
   // call DrainD2H() before reading wall-clock results.
   bool RangeBatchStart(const std::vector<DevRangeQ>& qs, std::string* err,
                        const std::string& qtails = std::string());
+  // Start also queues the batch's counter read-back into one of two pinned
+  // mirrors and records that slot's "results ready" event; range_slot() names
+  // the slot of the batch started last. Finish waits on its slot's event
+  // only, never on the stream, so batch i+1 may be started before batch i is
+  // finished (slot = the value range_slot() returned after batch i's Start;
+  // -1 = the batch started last). Only the counters are per slot: d2h needs
+  // the arena and therefore the latest batch.
   bool RangeBatchFinish(int nq, bool d2h, bool parse,
-                        std::vector<RangeResult>* outs, std::string* err);
+                        std::vector<RangeResult>* outs, std::string* err,
+                        int slot = -1);
+  int range_slot() const;
   bool DrainD2H(std::string* err);
+  // step staging block (stepstage.h): the get queries, range queries and key
+  // tails of one bench step go up in ONE H2D. Begin returns where to write
+  // nget + nrange queries and up to tail_cap tail bytes (pinned, double
+  // buffered; the ko offsets of both query kinds index the one tail slice).
+  // Commit queues the upload of the used span; the two Staged starts then
+  // launch over the staged slices exactly like GetBatchStart and
+  // RangeBatchStart (finish them with GetBatchFinish / RangeBatchFinish).
+  struct StepStage { DevGetQ* gq; DevRangeQ* rq; uint8_t* tails; int64_t tail_cap; };
+  bool StepStageBegin(int nget, int nrange, StepStage* st, std::string* err);
+  bool StepStageCommit(int64_t tail_bytes, std::string* err);
+  bool GetBatchStartStaged(std::string* err);
+  bool RangeBatchStartStaged(std::string* err);
   // batched List (kb_list_batch). RangeScanStart is the scan
   // half of RangeBatchStart alone (k_range_bounds + k_range_scan2): tagged
   // winner rows per query, no gather. ListSizeBatch runs it, then k_list_size
@@ -373,6 +404,11 @@ class Slab {
 
   struct Impl;
   Impl* p;
+
+ private:
+  bool launchScan(int nq, std::string* err);
+  bool launchGather(const DevRangeQ* hq, int nq, std::string* err);
+  bool launchGet(int nq, std::string* err);
 };
 
 }  // namespace kbslab

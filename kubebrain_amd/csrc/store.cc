@@ -163,7 +163,7 @@ uint64_t Store::stageSpill(const Bytes& key) {
   return off;
 }
 
-void Store::putRow(const Bytes& key, uint64_t rev, const Bytes& val) {
+void Store::putRow(const Bytes& key, uint64_t rev, std::string_view val) {
   NewRow r;
   r.key = key;
   r.rev = rev;
@@ -235,14 +235,15 @@ bool Store::syncReads(std::string* err) {
                 return a.rev < b.rev;
               });
     size_t m = newrows_.size();
-    std::vector<uint8_t> keys(m * KEYW);
-    std::vector<uint64_t> meta(m), rev(m), vo(m), ko(m);
+    // the sorted rows go straight into the slab's pinned upload mirror
+    kbslab::Slab::RowUpload up;
+    if (!slab_->BeginRowUpload((int64_t)m, &up, err)) return false;
     for (size_t i = 0; i < m; ++i) {
-      pad96(newrows_[i].key, keys.data() + i * KEYW);
-      meta[i] = newrows_[i].meta;
-      rev[i] = newrows_[i].rev;
-      vo[i] = newrows_[i].vo;
-      ko[i] = newrows_[i].ko;
+      pad96(newrows_[i].key, up.keys + i * KEYW);
+      up.meta[i] = newrows_[i].meta;
+      up.rev[i] = newrows_[i].rev;
+      up.vo[i] = newrows_[i].vo;
+      up.ko[i] = newrows_[i].ko;
     }
     // delta-merge drops happen exactly where an uploaded rev-row's key
     // already has a rev-row in the delta run — tracked host-side, so the
@@ -253,14 +254,12 @@ bool Store::syncReads(std::string* err) {
     }
     int64_t drops = 0;
     for (size_t i = 0; i < m; ++i) {
-      if (rev[i] != 0) continue;
+      if (newrows_[i].rev != 0) continue;
       auto ins = delta_revkeys_.insert(newrows_[i].key);
       if (!ins.second) drops++;
     }
     int64_t predicted = slab_->delta_rows() + (int64_t)m - drops;
-    if (!slab_->AppendRows(keys.data(), meta.data(), rev.data(), vo.data(),
-                           ko.data(), (int64_t)m, err, predicted))
-      return false;
+    if (!slab_->CommitRowUpload((int64_t)m, err, predicted)) return false;
     newrows_.clear();
     nr_revrow_.clear();
   }
@@ -287,7 +286,7 @@ bool Store::Flush(std::string* err) {
 
 // ---- events / watch -----------------------------------------------------
 
-void Store::notify(const Bytes& key, const Bytes& val, uint64_t revision,
+void Store::notify(const Bytes& key, std::string_view val, uint64_t revision,
                    uint64_t prevRevision, bool valid, Event::Type type) {
   // txn.go:267-293 + serial collector (backend.go:208-270): writes are
   // serialized, so events commit in ascending revision order in place.
@@ -299,7 +298,7 @@ void Store::notify(const Bytes& key, const Bytes& val, uint64_t revision,
   e.type = type;
   e.revision = revision;
   e.kv_key = key;
-  e.kv_value = val;
+  e.kv_value.assign(val.data(), val.size());
   e.kv_revision = type == Event::DELETE ? prevRevision : revision;
   if (keep_event_log_) event_log_.push_back(e);
   ring_.Add(e);  // backend.go:263 (ring keeps its own copy)
@@ -308,6 +307,13 @@ void Store::notify(const Bytes& key, const Bytes& val, uint64_t revision,
 }
 
 void Store::pumpEvents() {
+  // the watch entry points come through here and not through syncReads: like
+  // every other call from outside a bench step they first collect a batch a
+  // pipelined step left in flight
+  if (bench_pending_nq_ >= 0 && !in_bench_step_) {
+    std::string e;
+    if (!finishPendingBench(nullptr, &e)) { fatal_ = e; return; }
+  }
   if (pending_.empty()) return;
   const int64_t kBatch = 512;
   // seq of pending_[0]: the host ring and pending_ grow in lockstep (notify)
@@ -1861,6 +1867,64 @@ static void parseBenchQueries(const uint8_t* qbuf, size_t nq, uint64_t cur_rev,
   }
 }
 
+// tail of a bound or key longer than KEYW -> the step staging block's tail
+// slice at *used; false when the slice is full
+static bool stageTail(const uint8_t* b, size_t len, uint8_t* tails,
+                      int64_t tail_cap, int64_t* used, uint64_t* ko) {
+  *ko = 0;
+  if (len <= (size_t)KEYW) return true;
+  int64_t t = (int64_t)(len - KEYW);
+  if (t > tail_cap - *used) return false;
+  *ko = (uint64_t)*used;
+  memcpy(tails + *used, b + KEYW, (size_t)t);
+  *used += t;
+  return true;
+}
+
+static void pad96raw(const uint8_t* b, size_t len, uint8_t out[KEYW]) {
+  size_t n = std::min(len, (size_t)KEYW);
+  memcpy(out, b, n);
+  memset(out + n, 0, (size_t)KEYW - n);
+}
+
+// the same parse, written straight into the step staging block (pinned):
+// no query vector, no memcpy into the upload mirror
+static bool parseBenchQueriesStaged(const uint8_t* qbuf, size_t nq,
+                                    uint64_t cur_rev, int mode, DevRangeQ* qall,
+                                    std::vector<int64_t>* limits,
+                                    uint8_t* tails, int64_t tail_cap,
+                                    int64_t* tail_used) {
+  limits->resize(nq);
+  const int keys_only = (mode & 2) ? 1 : 0;
+  const uint8_t* p = qbuf;
+  for (size_t i = 0; i < nq; ++i) {
+    uint32_t slen, elen;
+    uint64_t rev, limit, ko;
+    memcpy(&slen, p, 4); p += 4;
+    memcpy(&elen, p, 4); p += 4;
+    memcpy(&rev, p, 8); p += 8;
+    memcpy(&limit, p, 8); p += 8;
+    DevRangeQ& q = qall[i];
+    pad96raw(p, slen, q.start);
+    if (!stageTail(p, slen, tails, tail_cap, tail_used, &ko)) return false;
+    q.start_klen = slen;
+    q.start_ko = ko;
+    p += slen;
+    pad96raw(p, elen, q.end);
+    if (!stageTail(p, elen, tails, tail_cap, tail_used, &ko)) return false;
+    q.end_klen = elen;
+    q.end_ko = ko;
+    p += elen;
+    q.read_rev = rev == 0 ? cur_rev : rev;
+    q.start_rev = 0;
+    q.cap = (int64_t)limit > 0 ? (int64_t)limit + 1 : 0;
+    q.count_only = 0;
+    q.keys_only = keys_only;
+    (*limits)[i] = (int64_t)limit;
+  }
+  return true;
+}
+
 bool Store::BenchRange(const uint8_t* qbuf, size_t nq, int mode,
                        unsigned long long* total, double* secs, std::string* err) {
   // the measured hot path: batched List semantics with inputs resident in HBM
@@ -1897,7 +1961,9 @@ bool Store::finishPendingBench(unsigned long long* total, std::string* err) {
     std::vector<kbslab::RangeResult> outs;
     int nq = bench_pending_nq_;
     bench_pending_nq_ = -1;
-    if (!slab_->RangeBatchFinish(nq, false, false, &outs, err)) return false;
+    if (!slab_->RangeBatchFinish(nq, false, false, &outs, err,
+                                 bench_pending_slot_))
+      return false;
     for (int j = 0; j < nq; ++j) {
       int64_t lim = bench_pending_limits_[j];
       int64_t w = outs[j].written;
@@ -1943,19 +2009,10 @@ bool Store::BenchStep(const uint8_t* qbuf, size_t nq, const uint8_t* tbuf,
   };
   if (!syncReads(err)) return false;
   lap("syncReads");
-  std::vector<DevRangeQ> qall;
-  std::vector<int64_t> limits;
-  std::string qtails;
-  parseBenchQueries(qbuf, nq, committed_, mode, &qall, &limits, &qtails);
-  lap("parse");
-  // pipelined (mode bit2): the previous step's range kernels ran while the
-  // host applied its txns and parsed this step; collect them now, return
-  // THEIR totals, and leave this step's batch in flight (range reads are
-  // snapshot-exact at their read_rev, so deferring collection never changes
-  // results)
+  // a batch a pipelined step left in flight is collected AFTER this step's
+  // batch is queued (below); a non-pipelined step collects it first
   unsigned long long prev_tot = 0;
-  if (pipe && !finishPendingBench(&prev_tot, err)) return false;
-  lap("finish_prev");
+  if (!pipe && !finishPendingBench(nullptr, err)) return false;
   // txn ops parsed up front so the batched CAS lookup (f1) can launch BEFORE
   // the range batch: stream order runs the small lookup first, the host
   // applies the conditional-update protocol against the device results while
@@ -1973,32 +2030,59 @@ bool Store::BenchStep(const uint8_t* qbuf, size_t nq, const uint8_t* tbuf,
       memcpy(&prev, p, 8); p += 8;
       memcpy(&vlen, p, 4); p += 4;
       tops[i].key.assign((const char*)p, klen); p += klen;
-      tops[i].val.assign((const char*)p, vlen); p += vlen;
+      tops[i].val = std::string_view((const char*)p, vlen); p += vlen;
       tops[i].prev = prev;
       if (tuniq && (!seen.insert(tops[i].key).second ||
                     validateKey(tops[i].key) != OK))
         tuniq = false;
     }
   }
-  auto t0 = std::chrono::steady_clock::now();
-  if (tuniq) {
-    std::vector<DevGetQ> gq(ntx);
-    std::string gtails;
-    for (size_t i = 0; i < ntx; ++i) {
-      gq[i] = DevGetQ{};
-      pad96(tops[i].key, gq[i].key);
-      gq[i].klen = (uint32_t)tops[i].key.size();
-      if (tops[i].key.size() > (size_t)KEYW) {
-        gq[i].ko = gtails.size();
-        gtails.append(tops[i].key.data() + KEYW, tops[i].key.size() - KEYW);
-      }
-      gq[i].read_rev = UINT64_MAX;
+  lap("txn_parse");
+  // get queries, range queries and their key tails are written in place
+  // into the slab's pinned step staging block: ONE upload for all three
+  const size_t nget = tuniq ? ntx : 0;
+  kbslab::Slab::StepStage stg;
+  if (!slab_->StepStageBegin((int)nget, (int)nq, &stg, err)) return false;
+  int64_t tail_used = 0;
+  for (size_t i = 0; i < nget; ++i) {
+    DevGetQ& g = stg.gq[i];
+    uint64_t ko;
+    const Bytes& k = tops[i].key;
+    pad96(k, g.key);
+    g.klen = (uint32_t)k.size();
+    g._pad = 0;
+    if (!stageTail((const uint8_t*)k.data(), k.size(), stg.tails, stg.tail_cap,
+                   &tail_used, &ko)) {
+      if (err) *err = "bench step: key tails exceed the staging block (KB_STAGE_TAIL_BYTES)";
+      return false;
     }
-    if (!slab_->GetBatchStart(gq, err, gtails)) return false;
+    g.ko = ko;
+    g.read_rev = UINT64_MAX;
   }
-  lap("txn_parse_getstart");
-  if (!slab_->RangeBatchStart(qall, err, qtails)) return false;
+  std::vector<int64_t> limits;
+  if (!parseBenchQueriesStaged(qbuf, nq, committed_, mode, stg.rq, &limits,
+                               stg.tails, stg.tail_cap, &tail_used)) {
+    if (err) *err = "bench step: key tails exceed the staging block (KB_STAGE_TAIL_BYTES)";
+    return false;
+  }
+  lap("parse");
+  auto t0 = std::chrono::steady_clock::now();
+  if (!slab_->StepStageCommit(tail_used, err)) return false;
+  if (!slab_->GetBatchStartStaged(err)) return false;
+  lap("stage_getstart");
+  if (!slab_->RangeBatchStartStaged(err)) return false;
+  const int cur_slot = slab_->range_slot();
   lap("range_start");
+  // pipelined (mode bit2): the previous step's range kernels ran while the
+  // host applied its txns and parsed this step. Collect them only now, with
+  // this step's batch already queued behind them, so the device never idles
+  // on the host: the wait is on the previous batch's own read-back event
+  // (stream order puts it ahead of every kernel of this batch). Return THEIR
+  // totals and leave this step's batch in flight (range reads are
+  // snapshot-exact at their read_rev, so deferring collection never changes
+  // results).
+  if (pipe && !finishPendingBench(&prev_tot, err)) return false;
+  lap("finish_prev");
   if (ntx > 0) {
     if (tuniq) {
       std::vector<kbslab::GetResult> cur;
@@ -2010,7 +2094,7 @@ bool Store::BenchStep(const uint8_t* qbuf, size_t nq, const uint8_t* tbuf,
       // duplicate keys: serial reference protocol (overlapped, host-only)
       for (size_t i = 0; i < ntx; ++i) {
         Status st;
-        auto r = Update(tops[i].key, tops[i].val, tops[i].prev, &st);
+        auto r = Update(tops[i].key, Bytes(tops[i].val), tops[i].prev, &st);
         if (st != OK) {
           if (err) *err = "bench txn failed st=" + std::to_string(st);
           return false;
@@ -2021,6 +2105,7 @@ bool Store::BenchStep(const uint8_t* qbuf, size_t nq, const uint8_t* tbuf,
   }
   if (pipe) {  // leave this step's batch in flight; report the previous one
     bench_pending_nq_ = (int)nq;
+    bench_pending_slot_ = cur_slot;
     bench_pending_limits_ = std::move(limits);
     *secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     *total = prev_tot;
@@ -2064,7 +2149,7 @@ bool Store::BenchTxn(const uint8_t* tbuf, size_t n, uint64_t* out_revs,
       memcpy(&prev, p, 8); p += 8;
       memcpy(&vlen, p, 4); p += 4;
       ops[i].key.assign((const char*)p, klen); p += klen;
-      ops[i].val.assign((const char*)p, vlen); p += vlen;
+      ops[i].val = std::string_view((const char*)p, vlen); p += vlen;
       ops[i].prev = prev;
       if (uniq && !seen.insert(ops[i].key).second) uniq = false;
     }
@@ -2073,7 +2158,7 @@ bool Store::BenchTxn(const uint8_t* tbuf, size_t n, uint64_t* out_revs,
   if (!uniq) {
     for (size_t i = 0; i < n; ++i) {
       Status st;
-      auto r = Update(ops[i].key, ops[i].val, ops[i].prev, &st);
+      auto r = Update(ops[i].key, Bytes(ops[i].val), ops[i].prev, &st);
       if (st != OK) {
         if (err) *err = "bench txn failed st=" + std::to_string(st);
         return false;

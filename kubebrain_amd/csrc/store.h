@@ -14,6 +14,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <string_view>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -164,15 +165,18 @@ class Store {
   uint64_t deal(uint64_t prevRevision, Status* st);
   uint64_t mustDeal(uint64_t prevRevision);
   Status createInternal(const Bytes& key, const Bytes& value, uint64_t revision);
-  void notify(const Bytes& key, const Bytes& val, uint64_t revision,
+  void notify(const Bytes& key, std::string_view val, uint64_t revision,
               uint64_t prevRevision, bool valid, Event::Type type);
   Status get(const Bytes& key, uint64_t revision, Bytes* val, uint64_t* modRev);
   Status checkCompactRace(uint64_t revision);
-  void putRow(const Bytes& key, uint64_t rev, const Bytes& val);
+  void putRow(const Bytes& key, uint64_t rev, std::string_view val);
   uint64_t stageSpill(const Bytes& key);  // stage a long key's tail
   void putRevRow(const Bytes& key, uint64_t objrev, bool flag9);
   void pumpEvents();  // fan-out pending events via the GPU filter
-  struct BatchOp { Bytes key, val; uint64_t prev; };
+  // val views the caller's packed txn blob, which outlives the call: the
+  // value bytes are copied where they are kept (heap staging, event), not
+  // once more on the way in
+  struct BatchOp { Bytes key; std::string_view val; uint64_t prev; };
   bool applyTxnOps(const BatchOp* ops, size_t cn,
                    const std::vector<kbslab::GetResult>& cur,
                    uint64_t* out_revs, std::string* err);
@@ -273,6 +277,7 @@ class Store {
   // overlap the host's txn apply + next-step prep. Valid only between
   // consecutive BenchStep calls; Sync() drains it.
   int bench_pending_nq_ = -1;
+  int bench_pending_slot_ = -1;  // Slab::range_slot() of the batch in flight
   bool in_bench_step_ = false;
   std::vector<int64_t> bench_pending_limits_;
   bool finishPendingBench(unsigned long long* total, std::string* err);
