@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "dmerge.h"
 #include "slab_dev.h"
 #include "stepstage.h"
 
@@ -147,6 +148,33 @@ __device__ int64_t d_lb_wave(const Run& r, const uint8_t* spill, int64_t n,
   return b ? lo + (__ffsll((unsigned long long)b) - 1) : hi;
 }
 
+// block-wide exclusive scan of one value per thread: shuffles inside each
+// wave, one LDS hop (wsum[blockDim.x / 64]) across waves, two barriers. Every
+// thread of the block must call; blockDim.x is a multiple of 64. *total =
+// the block's sum, in every thread. wsum may be reused after the call.
+template <typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T* wsum, T* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nw = blockDim.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    T o = __shfl_up(inc, off);
+    if (lane >= off) inc += o;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  T base = 0, tot = 0;
+  for (int i = 0; i < nw; ++i) {
+    T s = wsum[i];
+    if (i < w) base += s;
+    tot += s;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + inc - v;
+}
+
 // adjacent-row full-key equality (same spill both sides)
 __device__ __forceinline__ bool rows_same_key(const uint8_t* keys,
                                               const uint64_t* meta,
@@ -202,17 +230,43 @@ constexpr int SCAN_T_MAX = 1024;
 // delta — into one coalesced 8B stream read: base winner i is suppressed
 // iff shadow[i] != MAX && shadow[i] <= R (a strictly-newer delta row of the
 // key exists at or below the read revision).
-__global__ void k_shadow_mark(Run b, int64_t n, Run dnew, int64_t m,
-                              const uint8_t* __restrict__ spill,
-                              uint64_t* __restrict__ shadow) {
-  int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  uint64_t rv = dnew.rev[j];
+//
+// One wave per uploaded row (4 per 256-thread block): the 64-ary wave search
+// finds the key's first base row in ~5 round trips, one key compare confirms
+// it, and the key's run is then walked by its M_SAME_NEXT bits alone — 256
+// rows per round trip (four independent meta loads per lane), no key bytes.
+__global__ __launch_bounds__(256) void k_shadow_mark(
+    Run b, int64_t n, Run dnew, int64_t m, const uint8_t* __restrict__ spill,
+    uint64_t* __restrict__ shadow) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= m) return;  // wave-uniform from here on
+  const uint64_t rv = dnew.rev[j];
   if (rv == 0) return;  // rev-row holes never suppress
   QKey k = row_qk(dnew, spill, j);
-  for (int64_t i = d_lb_range(b, spill, 0, n, k, 1); i < n; ++i) {
-    if (rowcmp_q(b, spill, i, k) != 0) break;
-    atomicMin((unsigned long long*)&shadow[i], (unsigned long long)rv);
+  const int64_t lb = d_lb_wave(b, spill, n, k, 1);
+  if (lb >= n || rowcmp_q(b, spill, lb, k) != 0) return;  // no base row
+  for (int64_t c = lb; c < n; c += 256) {
+    uint64_t mm[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = c + u * 64 + lane;
+      mm[u] = i < n ? b.meta[i] : 0;  // 0: the run ends at or before row n-1
+    }
+    bool done = false;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (done) break;
+      const int64_t i = c + u * 64 + lane;
+      // lanes whose row is not followed by another row of the key; the first
+      // of them holds the run's last row (or lies past the run's end at n)
+      const uint64_t ends = __ballot(!(mm[u] & M_SAME_NEXT));
+      const int last = ends ? __ffsll((unsigned long long)ends) - 1 : 64;
+      if (lane <= last && i < n)
+        atomicMin((unsigned long long*)&shadow[i], (unsigned long long)rv);
+      done = ends != 0;
+    }
+    if (done) break;
   }
 }
 
@@ -563,67 +617,205 @@ __global__ void k_gather(Run b, Run d,
     overflow[q] = base_s > qcap ? 1 : 0;
     atomicAdd(bytes_out, (unsigned long long)(base_s <= qcap ? base_s : 0));
   }
-  // record copies happen in k_gather_copy (wider blocks, better latency
-  // hiding); this kernel only computes offsets/overflow
+  // record copies happen in k_gather_copy2; this kernel only computes
+  // offsets/overflow (KB_GATHER_MODE=2; mode 1 is k_gather_fused)
 }
 
-// copy winners' records into the arena; launched with 512 threads per query
-__global__ void k_gather_copy(Run rb, Run rd,
-                              const uint8_t* __restrict__ spill,
-                              const uint8_t* __restrict__ heap,
-                              const uint64_t* __restrict__ rows_out,
-                              int64_t max_cap,
-                              const int64_t* __restrict__ found_out,
-                              const DevRangeQ* __restrict__ qs, int nq,
-                              uint8_t* __restrict__ gbuf, int64_t qcap,
-                              const int64_t* __restrict__ offs,
-                              const int32_t* __restrict__ overflow,
-                              int gwl) {  // log2(record-group lanes), KB_GATHER_GW
-  int q = blockIdx.x;
-  if (q >= nq || overflow[q]) return;
-  int64_t nwin = found_out[q];
+// ---- fused gather (KB_GATHER_MODE=1): offsets + copy in one kernel ---------
+// One block per query. Winners are taken in chunks of GATHER_CH:
+//   resolve: one thread per winner reads rows[j], then meta/rev/vo[row] — the
+//     whole chunk's chains run side by side, two round trips — and a shuffle
+//     scan of the record sizes leaves {row, rev, vo, klen|vlen, arena offset}
+//     per winner in LDS;
+//   copy: lane groups of 2^gwl lanes move records with every address taken
+//     from LDS, one global round trip per record (columns/heap -> arena),
+//     two records in flight per group (both records' loads before either's
+//     stores).
+// The overflow decision needs the query's total: a query of <= GATHER_CH
+// winners (every capped bench query) is resolved once and the total falls out
+// of its scan; a longer one is sized in a pass of its own first and then
+// resolved chunk by chunk. Writes exactly the bytes k_gather + k_gather_copy
+// wrote; the per-winner offsets live in LDS only.
+constexpr int GATHER_CH = 512;  // 5 x 8 B x 512 = 20 KB of LDS
+constexpr int GATHER_KR = 2;    // key u64 rounds per lane held in registers
+constexpr int GATHER_VR = 4;    // value uint4 rounds per lane held in registers
+
+// 16 B in one register quad (a native vector: stays out of scratch)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct GatherLds {
+  uint64_t row[GATHER_CH];  // tagged winner row
+  uint64_t rev[GATHER_CH];
+  uint64_t vo[GATHER_CH];   // heap offset of the value
+  uint64_t kv[GATHER_CH];   // klen | vlen << 32 (vlen 0 when keys-only)
+  int64_t dst[GATHER_CH];   // record offset inside the query's arena share
+  int64_t ws[16];           // block_excl_scan's per-wave sums
+};
+
+// winners [c0, c0+cn) of the query -> LDS; returns base + their bytes
+__device__ __forceinline__ int64_t gather_resolve(
+    const Run& rb, const Run& rd, const uint64_t* __restrict__ rows,
+    int64_t c0, int cn, bool konly, int64_t base, GatherLds& L) {
+  for (int s0 = 0; s0 < cn; s0 += blockDim.x) {  // block-uniform trip count
+    const int s = s0 + threadIdx.x;
+    uint64_t rt = 0, rv = 0, vo = 0, kv = 0;
+    int64_t sz = 0;
+    if (s < cn) {
+      rt = rows[c0 + s];
+      const Run& r = (rt & ROW_TAG_DELTA) ? rd : rb;
+      const int64_t row = (int64_t)(rt & ROW_MASK);
+      const uint64_t m = r.meta[row];
+      rv = r.rev[row];
+      vo = r.vo[row];
+      const uint32_t klen = meta_klen(m), vlen = konly ? 0 : meta_vlen(m);
+      kv = (uint64_t)klen | ((uint64_t)vlen << 32);
+      sz = rec_bytes(klen, vlen);
+    }
+    int64_t tot;
+    const int64_t ex = block_excl_scan<int64_t>(sz, L.ws, &tot);
+    if (s < cn) {
+      L.row[s] = rt;
+      L.rev[s] = rv;
+      L.vo[s] = vo;
+      L.kv[s] = kv;
+      L.dst[s] = base + ex;
+    }
+    base += tot;
+  }
+  return base;
+}
+
+// the LDS chunk's cn records -> arena
+__device__ __forceinline__ void gather_copy_chunk(
+    const Run& rb, const Run& rd, const uint8_t* __restrict__ spill,
+    const uint8_t* __restrict__ heap, uint8_t* __restrict__ qb, int cn,
+    int gwl, const GatherLds& L) {
+  const int gw = 1 << gwl, gpw = 64 >> gwl;  // lanes per group, groups per wave
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int grp = lane >> gwl, gl = lane & (gw - 1);
+  const int stride = (blockDim.x >> 6) * gpw;
+  for (int s = w * gpw + grp; s < cn; s += 2 * stride) {
+    bool ok[2];
+    const uint8_t *ks[2], *vs[2];
+    uint8_t* dst[2];
+    uint32_t klen[2], vlen[2], kw[2], w16[2];
+    uint64_t kreg[2][GATHER_KR];
+    u32x4 vreg[2][GATHER_VR];
+    // loads of both records first ...
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int su = s + u * stride;
+      ok[u] = su < cn;
+      if (!ok[u]) continue;
+      const uint64_t rt = L.row[su], kv = L.kv[su];
+      const Run& r = (rt & ROW_TAG_DELTA) ? rd : rb;
+      ks[u] = r.keys + (int64_t)(rt & ROW_MASK) * KEYW;
+      vs[u] = heap + L.vo[su];
+      dst[u] = qb + L.dst[su];
+      klen[u] = (uint32_t)kv;
+      vlen[u] = (uint32_t)(kv >> 32);
+      const uint32_t kin = klen[u] > (uint32_t)KEYW ? (uint32_t)KEYW : klen[u];
+      // column rows are 96B-strided => 8-aligned; whole u64s (may round up
+      // to 7B into the record's 16B key padding — always in-bounds)
+      kw[u] = (kin + 7) / 8;
+      w16[u] = vlen[u] >> 4;
+#pragma unroll
+      for (int t = 0; t < GATHER_KR; ++t) {
+        const uint32_t b = gl + t * gw;
+        if (b < kw[u]) kreg[u][t] = ((const uint64_t*)ks[u])[b];
+      }
+#pragma unroll
+      for (int t = 0; t < GATHER_VR; ++t) {
+        const uint32_t b = gl + t * gw;
+        if (b < w16[u]) vreg[u][t] = ((const u32x4*)vs[u])[b];
+      }
+    }
+    // ... then the stores, and whatever the register rounds did not cover
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (!ok[u]) continue;
+      const int su = s + u * stride;
+      if (gl == 0) {
+        ((uint64_t*)dst[u])[0] = L.rev[su];
+        ((uint64_t*)dst[u])[1] = (uint64_t)klen[u] | ((uint64_t)vlen[u] << 32);
+      }
+      uint8_t* kd = dst[u] + 16;  // records are 16B-aligned
+      uint8_t* vd = kd + ((klen[u] + 15) & ~15u);
+#pragma unroll
+      for (int t = 0; t < GATHER_KR; ++t) {
+        const uint32_t b = gl + t * gw;
+        if (b < kw[u]) ((uint64_t*)kd)[b] = kreg[u][t];
+      }
+#pragma unroll
+      for (int t = 0; t < GATHER_VR; ++t) {
+        const uint32_t b = gl + t * gw;
+        if (b < w16[u]) ((u32x4*)vd)[b] = vreg[u][t];
+      }
+      for (uint32_t b = gl + GATHER_KR * gw; b < kw[u]; b += gw)
+        ((uint64_t*)kd)[b] = ((const uint64_t*)ks[u])[b];
+      for (uint32_t b = gl + GATHER_VR * gw; b < w16[u]; b += gw)
+        ((u32x4*)vd)[b] = ((const u32x4*)vs[u])[b];
+      if (klen[u] > (uint32_t)KEYW) {  // spill tail (keys > 96B)
+        const uint64_t rt = L.row[su];
+        const Run& r = (rt & ROW_TAG_DELTA) ? rd : rb;
+        const uint8_t* ts = spill + r.ko[rt & ROW_MASK];
+        for (uint32_t t = gl; t < klen[u] - (uint32_t)KEYW; t += gw)
+          kd[KEYW + t] = ts[t];
+      }
+      if (gl == 0)
+        for (uint32_t b = w16[u] * 16; b < vlen[u]; ++b) vd[b] = vs[u][b];
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_gather_fused(
+    Run rb, Run rd, const uint8_t* __restrict__ spill,
+    const uint8_t* __restrict__ heap, const uint64_t* __restrict__ rows_out,
+    int64_t max_cap, const int64_t* __restrict__ found_out,
+    const DevRangeQ* __restrict__ qs, int nq, uint8_t* __restrict__ gbuf,
+    int64_t qcap, int64_t* __restrict__ gbytes_out,
+    int32_t* __restrict__ overflow, unsigned long long* __restrict__ bytes_out,
+    int gwl) {
+  __shared__ GatherLds L;
+  const int q = blockIdx.x;
+  if (q >= nq) return;
+  const int64_t nwin = found_out[q];
   const bool konly = qs[q].keys_only != 0;
   const uint64_t* rows = rows_out + (int64_t)q * max_cap;
-  const int64_t* qoffs = offs + (int64_t)q * max_cap;
-  // record groups of 2^gwl lanes — independent load chains across records
-  const int gw = 1 << gwl, gpw = 64 >> gwl;  // lanes per group, groups per wave
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int grp = lane >> gwl, gl = lane & (gw - 1);
+  const bool single = nwin <= GATHER_CH;
+  int64_t total = 0;
+  if (single) {
+    total = gather_resolve(rb, rd, rows, 0, (int)nwin, konly, 0, L);
+  } else {  // size every winner first: the total decides overflow
+    int64_t loc = 0;
+    for (int64_t j = threadIdx.x; j < nwin; j += blockDim.x) {
+      const uint64_t rt = rows[j];
+      const uint64_t m =
+          ((rt & ROW_TAG_DELTA) ? rd.meta : rb.meta)[rt & ROW_MASK];
+      loc += rec_bytes(meta_klen(m), konly ? 0 : meta_vlen(m));
+    }
+    (void)block_excl_scan<int64_t>(loc, L.ws, &total);
+  }
+  const bool ovf = total > qcap;  // block-uniform
+  if (threadIdx.x == 0) {
+    gbytes_out[q] = total;
+    overflow[q] = ovf ? 1 : 0;
+    atomicAdd(bytes_out, (unsigned long long)(ovf ? 0 : total));
+  }
+  if (ovf) return;  // an overflowing query writes no record bytes
   uint8_t* qb = gbuf + (int64_t)q * qcap;
-  int64_t stride = (blockDim.x / 64) * gpw;
-  for (int64_t j = (int64_t)w * gpw + grp; j < nwin; j += stride) {
-    uint64_t rt = rows[j];
-    bool isd = (rt & ROW_TAG_DELTA) != 0;
-    int64_t row = (int64_t)(rt & ROW_MASK);
-    const Run& r = isd ? rd : rb;
-    uint64_t m = r.meta[row];
-    uint32_t klen = meta_klen(m), vlen = konly ? 0 : meta_vlen(m);
-    uint8_t* dst = qb + qoffs[j];
-    if (gl == 0) {
-      *(uint64_t*)dst = r.rev[row];
-      ((uint32_t*)dst)[2] = klen;
-      ((uint32_t*)dst)[3] = vlen;
-    }
-    const uint8_t* ks = r.keys + row * KEYW;
-    uint8_t* kd = dst + 16;  // 8-aligned (records are 16B-aligned)
-    uint32_t kin = klen > (uint32_t)KEYW ? (uint32_t)KEYW : klen;
-    // column rows are 96B-strided => 8-aligned; copy whole u64s (may round
-    // up to 7B into the record's 16B key padding — always in-bounds)
-    for (uint32_t b = gl; b < (kin + 7) / 8; b += gw)
-      ((uint64_t*)kd)[b] = ((const uint64_t*)ks)[b];
-    if (klen > (uint32_t)KEYW) {  // spill tail (keys > 96B)
-      const uint8_t* ts = spill + r.ko[row];
-      for (uint32_t t = gl; t < klen - (uint32_t)KEYW; t += gw)
-        kd[KEYW + t] = ts[t];
-    }
-    if (konly) continue;
-    const uint8_t* vs = heap + r.vo[row];
-    uint8_t* vd = dst + 16 + ((klen + 15) & ~15u);
-    uint32_t w16 = vlen >> 4;
-    for (uint32_t b = gl; b < w16; b += gw)
-      ((uint4*)vd)[b] = ((const uint4*)vs)[b];
-    if (gl == 0)
-      for (uint32_t b = w16 * 16; b < vlen; ++b) vd[b] = vs[b];
+  if (single) {
+    __syncthreads();
+    gather_copy_chunk(rb, rd, spill, heap, qb, (int)nwin, gwl, L);
+    return;
+  }
+  int64_t base = 0;
+  for (int64_t c0 = 0; c0 < nwin; c0 += GATHER_CH) {
+    const int cn = (int)(nwin - c0 < GATHER_CH ? nwin - c0 : GATHER_CH);
+    base = gather_resolve(rb, rd, rows, c0, cn, konly, base, L);
+    __syncthreads();
+    gather_copy_chunk(rb, rd, spill, heap, qb, cn, gwl, L);
+    __syncthreads();  // the next resolve overwrites the chunk
   }
 }
 
@@ -851,62 +1043,93 @@ __global__ void k_heap_scatter(const uint64_t* __restrict__ keep,
 }
 
 // ---- merge (memtable flush): delta ranks + scatter ----------------------
-// inverted small-insert merge (m <= 1024 new rows into an n-row run): ONE
-// block searches each NEW row into the big run — m*log2(n) work instead of
-// k_merge_rank's n*log2(m) — writes the new rows at their final slots, and
-// leaves a difference array v[0..n+1] whose prefix sum is each base row's
-// slot shift (insertions +1 at ub_j, drops -1 after lb_j). drop[] marks
-// replaced base rows ((key,rev)-equal memtable revision-rows). new_n -> s_d.
-__global__ void k_merge_insert_inv(
+// small-insert merge (m <= 1024 new rows into an n-row run, the per-step txn
+// merge), two kernels and no O(n) scratch. k_delta_rank: one wave per NEW
+// row searches the run with the 64-ary wave search (m*log64(n) round trips)
+// and leaves its insertion point lb[j] and whether the row there is
+// (key,rev)-equal (dup[j]: a memtable revision-row replaces it).
+__global__ __launch_bounds__(256) void k_delta_rank(
     Run a, int64_t n, Run dnew, int64_t m, const uint8_t* __restrict__ spill,
-    uint64_t* __restrict__ v /*[n+2] zeroed*/,
-    uint64_t* __restrict__ drop /*[n] zeroed*/,
-    uint64_t* __restrict__ outpos /*[m] delta dest slots (for the fixup)*/,
-    uint8_t* keysB, uint64_t* metaB, uint64_t* revB, uint64_t* voB,
-    uint64_t* koB, int64_t* __restrict__ newn_out) {
-  __shared__ uint16_t ldup[1024];
-  int64_t j = threadIdx.x;
-  bool has = j < m;
-  int64_t lb = n;
-  bool dup = false;
-  if (has) {
-    QKey k = row_qk(dnew, spill, j);
-    lb = d_lb_range(a, spill, 0, n, k, dnew.rev[j]);
-    dup = lb < n && a.rev[lb] == dnew.rev[j] &&
-          rowcmp_q(a, spill, lb, k) == 0;
+    int64_t* __restrict__ lbs /*[m]*/, uint32_t* __restrict__ dups /*[m]*/) {
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= m) return;  // wave-uniform
+  QKey k = row_qk(dnew, spill, j);
+  const uint64_t rv = dnew.rev[j];
+  const int64_t lb = d_lb_wave(a, spill, n, k, rv);
+  const bool dup = lb < n && a.rev[lb] == rv && rowcmp_q(a, spill, lb, k) == 0;
+  if ((threadIdx.x & 63) == 0) {
+    lbs[j] = lb;
+    dups[j] = dup ? 1 : 0;
   }
-  ldup[threadIdx.x] = dup ? 1 : 0;
-  __syncthreads();
-  // exclusive prefix of dup flags over the block (m <= 1024)
-  int64_t dupx = 0, total = 0;
-  for (int t = 0; t < (int)m; ++t) {
-    if (t < (int)j) dupx += ldup[t];
-    total += ldup[t];
-  }
-  if (threadIdx.x == 0 && newn_out) *newn_out = n + m - total;
-  if (!has) return;
-  if (dup) {
-    drop[lb] = 1;
-    atomicAdd(&v[lb + 1], (uint64_t)-1ll);
-  }
-  atomicAdd(&v[lb + (dup ? 1 : 0)], 1ull);  // ub_j = lb + dup
-  int64_t out = lb - dupx + j;
-  outpos[j] = (uint64_t)out;
-  revB[out] = dnew.rev[j];
-  metaB[out] = dnew.meta[j];
-  voB[out] = dnew.vo[j];
-  koB[out] = dnew.ko[j];
-  const uint4* ks = (const uint4*)(dnew.keys + j * KEYW);
+}
+
+__device__ __forceinline__ void copy_row(const Run& s, int64_t i,
+                                         uint8_t* keysB, uint64_t* metaB,
+                                         uint64_t* revB, uint64_t* voB,
+                                         uint64_t* koB, int64_t out) {
+  revB[out] = s.rev[i];
+  metaB[out] = s.meta[i];
+  voB[out] = s.vo[i];
+  koB[out] = s.ko[i];
+  const uint4* ks = (const uint4*)(s.keys + i * KEYW);
   uint4* kd = (uint4*)(keysB + out * KEYW);
 #pragma unroll
   for (int t = 0; t < KEYW / 16; ++t) kd[t] = ks[t];
 }
 
+// k_delta_scatter: one thread per old row plus one per new row. Every block
+// keeps lb[0,m) and the exclusive prefix of dup[0,m] in LDS; the m insertion
+// points are monotone, so an old row finds its shift with two ~10-step
+// binary searches there (dmerge.h) instead of a difference array, two
+// memsets and a multi-level scan over n. New rows record their slot in
+// outpos for the same_next fixup. new_n -> newn_out (s_d).
+__global__ __launch_bounds__(256) void k_delta_scatter(
+    Run a, int64_t n, Run dnew, int64_t m,
+    const int64_t* __restrict__ lbs, const uint32_t* __restrict__ dups,
+    uint64_t* __restrict__ outpos /*[m] new rows' slots*/,
+    uint8_t* keysB, uint64_t* metaB, uint64_t* revB, uint64_t* voB,
+    uint64_t* koB, int64_t* __restrict__ newn_out) {
+  __shared__ int64_t s_lb[kbmerge::kMaxNew];
+  __shared__ uint16_t s_dupx[kbmerge::kMaxNew + 4];
+  __shared__ uint32_t s_ws[4];
+  const int t = threadIdx.x, mi = (int)m;
+  for (int x = t; x < mi; x += 256) s_lb[x] = lbs[x];
+  // thread t owns dup[4t, 4t+4): 256 threads cover the 1024 possible rows
+  uint32_t d[4], sum = 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    d[u] = 4 * t + u < mi ? dups[4 * t + u] : 0;
+    sum += d[u];
+  }
+  uint32_t tot;
+  uint32_t run = block_excl_scan<uint32_t>(sum, s_ws, &tot);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (4 * t + u < mi) s_dupx[4 * t + u] = (uint16_t)run;
+    run += d[u];
+  }
+  if (t == 0) s_dupx[mi] = (uint16_t)tot;  // entry m: no thread owns it at m = 1024
+  __syncthreads();
+  const int64_t g = (int64_t)blockIdx.x * 256 + t;
+  if (g < n) {
+    const int64_t out = kbmerge::OldSlot(g, s_lb, s_dupx, mi);
+    if (out >= 0) copy_row(a, g, keysB, metaB, revB, voB, koB, out);
+  } else if (g < n + m) {
+    const int j = (int)(g - n);
+    const int64_t out = kbmerge::NewSlot(j, s_lb, s_dupx);
+    outpos[j] = (uint64_t)out;
+    copy_row(dnew, j, keysB, metaB, revB, voB, koB, out);
+  }
+  if (g == 0) *newn_out = kbmerge::NewCount(n, mi, s_dupx);
+}
+
 // multi-block inverted merge rank (any m into n>0 rows): each NEW row
 // binary-searches the big run once — m*log2(n) probes instead of the
-// forward path's n*log2(m) — and leaves the same difference array v as the
-// single-block variant. dup flags go to dup[] (scanned separately to give
-// each new row its drops-before count).
+// forward path's n*log2(m) — and leaves a difference array v[0..n+1] whose
+// prefix sum is each base row's slot shift (insertions +1 at ub_j, drops -1
+// after lb_j). drop[] marks replaced base rows ((key,rev)-equal memtable
+// revision-rows); dup flags go to dup[] (scanned separately to give each
+// new row its drops-before count).
 __global__ void k_merge_rank_inv_big(Run a, int64_t n, Run dnew, int64_t m,
                                      const uint8_t* __restrict__ spill,
                                      uint64_t* __restrict__ v /*[n+2] zeroed*/,
@@ -1660,7 +1883,7 @@ struct Slab::Impl {
 
   // scan scratch (u64, shared across ops)
   uint64_t* shadow = nullptr;  // [max_rows] base shadow-revision column
-  uint64_t* d_outpos = nullptr;  // [1024] inverted-insert dest slots
+  uint64_t* d_outpos = nullptr;  // small insert: [1024] dest slots | lb | dup
   // big inverted merge scratch: dup flags / their scan / new-row lower
   // bounds (then final slots), all m-sized, grown on demand
   uint64_t *d_mdup = nullptr, *d_mdupx = nullptr, *d_mlbs = nullptr;
@@ -1716,7 +1939,7 @@ struct Slab::Impl {
   int scan_t = 1024;            // KB_SCAN_T: threads per scan block
   int gather_gwl = 4;           // KB_GATHER_GW: log2 lanes per record group
   int gather_t = 512;           // KB_GATHER_T: threads per gather_copy block
-  int gather_mode = 1;          // KB_GATHER_MODE: 1=record groups, 2=wave/record
+  int gather_mode = 1;          // KB_GATHER_MODE: 1=fused record groups, 2=wave/record
   int64_t max_cap = 4352;       // winners per query cap (>= limit+1 for etcd's 500)
   int64_t arena_bytes = 384ll << 20;
   DevRangeQ* d_qs = nullptr;
@@ -2111,19 +2334,21 @@ struct Slab::Impl {
     }
     if (m > 0 && m <= 1024 && n > 0) {
       // inverted small-insert path (the per-step txn merge): m searches into
-      // the n-row run, not n searches into the m new rows
+      // the n-row run, not n searches into the m new rows; rank, scatter,
+      // fixup — three launches, no scratch beyond 3 x 1024 entries
       perf->merge_insert++;
-      if (!d_outpos) HIP_CHECK(hipMalloc(&d_outpos, 1024 * 8));
-      HIP_CHECK(hipMemsetAsync(s_a, 0, (n + 2) * 8, stream));
-      HIP_CHECK(hipMemsetAsync(s_b, 0, n * 8, stream));
-      hipLaunchKernelGGL(k_merge_insert_inv, dim3(1), dim3(1024), 0, stream,
-                         src.run(), n, dnew, m, spillA, s_a, s_b, d_outpos,
+      static_assert(kbmerge::kMaxNew == 1024, "small-insert bound");
+      if (!d_outpos) HIP_CHECK(hipMalloc(&d_outpos, 1024 * (8 + 8 + 4)));
+      int64_t* d_lbs = (int64_t*)(d_outpos + 1024);
+      uint32_t* d_dups = (uint32_t*)(d_outpos + 2048);
+      hipLaunchKernelGGL(k_delta_rank, dim3((uint32_t)ceil_div(m, 4)),
+                         dim3(256), 0, stream, src.run(), n, dnew, m, spillA,
+                         d_lbs, d_dups);
+      hipLaunchKernelGGL(k_delta_scatter,
+                         dim3((uint32_t)ceil_div(n + m, 256)), dim3(256), 0,
+                         stream, src.run(), n, dnew, m, d_lbs, d_dups, d_outpos,
                          dst.keys, dst.meta, dst.rev, dst.vo, dst.ko,
                          (int64_t*)s_d);
-      if (!scan(s_a, s_c, n + 2, nullptr, err)) return false;  // no host sync
-      hipLaunchKernelGGL(k_merge_scatter_base2, dim3((uint32_t)ceil_div(n, 256)),
-                         dim3(256), 0, stream, src.run(), s_c, s_b, dst.keys,
-                         dst.meta, dst.rev, dst.vo, dst.ko, n);
       int64_t new_n;
       if (device_newn_ok) {
         new_n = *out_n;
@@ -2502,7 +2727,7 @@ bool Slab::CommitRowUpload(int64_t m, std::string* err, int64_t known_new_dn) {
   // kernels queue (same stream => ordering is irrelevant, both read only
   // the base run and the upload)
   if (I->n > 0)
-    hipLaunchKernelGGL(k_shadow_mark, dim3((uint32_t)ceil_div(m, 256)),
+    hipLaunchKernelGGL(k_shadow_mark, dim3((uint32_t)ceil_div(m, 4)),
                        dim3(256), 0, I->stream, I->A.run(), I->n, up, m,
                        I->spillA, I->shadow);
   if (!I->mergeRuns(I->DA, I->dn, up, m, I->DB, &new_dn, err,
@@ -2677,11 +2902,11 @@ bool Slab::launchGather(const DevRangeQ* hq, int nq, std::string* err) {
   const int rs = I->rb_slot;
   int64_t qcap = I->arena_bytes / nq;
   qcap &= ~15ll;
-  hipLaunchKernelGGL(k_gather, dim3(nq), dim3(256), 0, I->stream, I->A.run(),
-                     I->DA.run(), I->heapA, I->d_rowsm, I->max_cap,
-                     I->d_found, I->d_qs, nq, I->d_gbuf, qcap, I->d_offs,
-                     I->d_gbytes, I->d_ovf, I->d_bytes);
   if (I->gather_mode == 2) {
+    hipLaunchKernelGGL(k_gather, dim3(nq), dim3(256), 0, I->stream, I->A.run(),
+                       I->DA.run(), I->heapA, I->d_rowsm, I->max_cap,
+                       I->d_found, I->d_qs, nq, I->d_gbuf, qcap, I->d_offs,
+                       I->d_gbytes, I->d_ovf, I->d_bytes);
     int64_t maxw = 0;
     for (int i = 0; i < nq; ++i) {
       int64_t qc = hq[i].cap;  // packed struct: copy, do not bind
@@ -2694,10 +2919,12 @@ bool Slab::launchGather(const DevRangeQ* hq, int nq, std::string* err) {
                        I->d_rowsm, I->max_cap, I->d_found, I->d_qs, nq,
                        I->d_gbuf, qcap, I->d_offs, I->d_ovf);
   } else {
-    hipLaunchKernelGGL(k_gather_copy, dim3(nq), dim3((uint32_t)I->gather_t), 0, I->stream,
-                       I->A.run(), I->DA.run(), I->spillA, I->heapA, I->d_rowsm,
-                       I->max_cap, I->d_found, I->d_qs, nq, I->d_gbuf, qcap,
-                       I->d_offs, I->d_ovf, I->gather_gwl);
+    // offsets, overflow, byte counters and the copy in one launch
+    hipLaunchKernelGGL(k_gather_fused, dim3(nq), dim3((uint32_t)I->gather_t), 0,
+                       I->stream, I->A.run(), I->DA.run(), I->spillA, I->heapA,
+                       I->d_rowsm, I->max_cap, I->d_found, I->d_qs, nq,
+                       I->d_gbuf, qcap, I->d_gbytes, I->d_ovf, I->d_bytes,
+                       I->gather_gwl);
   }
   HIP_CHECK(hipEventRecord(I->ev_r2[rs], I->stream));
   // found/total/gbytes/ovf/scanned/bytes share one device block: one D2H

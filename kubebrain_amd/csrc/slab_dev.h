@@ -134,7 +134,7 @@ struct Perf {
   double get_batch_ms = 0, get_batch_d2h_ms = 0;
   int64_t get_batch_calls = 0, get_batch_q_dev = 0, get_batch_q_host = 0,
           get_batch_found = 0, get_batch_bytes = 0, get_batch_launches = 0;
-  // which mergeRuns branch ran (k_merge_small / k_merge_insert_inv /
+  // which mergeRuns branch ran (k_merge_small / k_delta_rank + k_delta_scatter /
   // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
   // async no-sync branch, and delta->base folds: the tests prove with these
   // that a workload reached the path it claims to cover
