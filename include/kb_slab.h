@@ -174,6 +174,49 @@ int kb_test_get_plan(const int* has_kv, const unsigned long long* vlen,
 /* backend.Count (range.go:177-205) */
 int kb_count(kb_store*, const uint8_t* start, size_t slen, const uint8_t* end,
              size_t elen, uint64_t* header_rev, uint64_t* count);
+/* n Counts in one call (range.go:177-205 per query), one mutex hold.
+ * qbuf = the blob kb_list_batch / kb_bench_range take: n x {u32 slen; u32
+ * elen; u64 rev; i64 limit; start; end}. limit is ignored: a count is the
+ * total in range whatever the limit is. rev == 0 means latest.
+ * out = u32 n; n x {i32 status; i32 0; u64 header_rev; u64 count} = 4 + 24 n
+ * bytes. header_rev is the committed revision at the call, the same in every
+ * entry. For rev == 0, status and count are EXACTLY what kb_count(start,
+ * end) returns at that moment: its validation of both bounds (KB_EBADKEY,
+ * KB_EKEYTOOLONG) and its compaction check, not kb_list's extra checks —
+ * start >= end or an empty end is KB_OK with whatever kb_count counts
+ * (normally 0). For rev != 0 (an extension: the reference's Count ignores
+ * RangeRequest.Revision, etcd3 honours it) validation is the same, the
+ * compaction check is made against rev (KB_ECOMPACTED as kb_list gives it)
+ * and count is the number of kvs an unbounded kb_list(start, end, rev)
+ * returns. A non-OK entry has count 0 and never fails the call. With
+ * enable_etcd_compatibility == 0 every entry is KB_OK with count 0 and no
+ * kernel runs (range.go:188-193).
+ * flags must be 0, else KB_EINVALID. KB_ENOBUF (cap < 4 + 24 n): *out_len =
+ * required size, nothing is written. n == 0 is valid (out = u32 0); n above
+ * KB_MAX_Q is served in sub-batches inside the call. *total_count = sum of
+ * the counts.
+ * Every range is cut into tiles of KB_COUNT_TILE rows (a multiple of 64, at
+ * least 64, default 4096) that HIP kernels count across the whole chip
+ * (DESIGN.md §3.8). May be interleaved freely with every other call; a
+ * pending pipelined kb_bench_step batch is collected first. The call writes
+ * neither the winner tables nor the gather arena: kb_test_last_range returns
+ * after it exactly the bytes it returned before it. */
+int kb_count_batch(kb_store*, const uint8_t* qbuf, size_t n, int flags,
+                   uint8_t* out, size_t cap, size_t* out_len,
+                   unsigned long long* total_count);
+/* TEST-ONLY: the pure tile map of kb_count_batch (no GPU, no store).
+ * bounds = nq x {lo, hi, dlo, dhi}: per query the row range of the base run
+ * and of the delta run, i.e. 2 nq segments; inverted bounds (lo > hi) hold no
+ * row. tile = rows per tile (a multiple of 64, at least 64, else
+ * KB_EINVALID). Outputs (caller arrays, may be NULL): pfx[2 nq + 1] = the
+ * exclusive prefix of the segments' tile counts; per tile id its query, run
+ * (0 base, 1 delta) and rows [r0, r1) (room for tile_cap tiles); *n_tiles.
+ * Returns KB_OK, or KB_ENOBUF (*n_tiles > tile_cap: only pfx and *n_tiles
+ * are written). */
+int kb_test_count_plan(const long long* bounds, size_t nq, long long tile,
+                       unsigned long long* pfx, int* t_query, int* t_run,
+                       long long* t_r0, long long* t_r1, size_t tile_cap,
+                       size_t* n_tiles);
 
 /* ---- compaction (compact.go:31-127 + scanner.go:444-491,566-591) ---- */
 int kb_compact(kb_store*, uint64_t rev, uint64_t* out_rev);

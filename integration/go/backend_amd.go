@@ -388,6 +388,79 @@ func (b *amdBackend) Count(ctx context.Context, r *proto.CountRequest) (*proto.C
 		Count: uint64(cnt)}, nil
 }
 
+// CountQuery is one Count of a batched Count: Revision 0 means latest.
+type CountQuery struct {
+	Key, End []byte
+	Revision uint64
+}
+
+// CountResult is one query's share of a batched Count: Err is what Count
+// would have returned for that query alone (nil, or the error of KB_EBADKEY /
+// KB_EKEYTOOLONG / KB_ECOMPACTED), Resp its count.
+type CountResult struct {
+	Err  error
+	Resp *proto.CountResponse
+}
+
+// CountBatch serves many Counts with ONE kb_count_batch call: one mutex hold,
+// one header revision, every range cut into row tiles that the GPU counts
+// across all its compute units (DESIGN.md §3.8). A kube-apiserver sends one
+// CountOnly Range per resource type for its object-count metrics and one per
+// paged List for remainingItemCount; a host collects them and calls this from
+// one goroutine. Unlike Count, a query may name a read revision (etcd3
+// honours RangeRequest.Revision on CountOnly; the reference ignores it). Same
+// ENOBUF contract as every other call, though a buffer of 4 + 24 n bytes
+// always fits. buf may be nil; the (possibly grown) buffer is returned.
+// Not part of the Backend interface, and like the rest of this file it has
+// not been seen by a Go compiler (see the NOTE at the top); the executable
+// specification of the request and reply formats is kubebrain_amd/client.py
+// encode_queries / count_batch + tests/test_gpu_count_batch.py.
+func (b *amdBackend) CountBatch(qs []CountQuery, buf []byte) ([]CountResult, []byte, error) {
+	if len(buf) < 4+24*len(qs) {
+		buf = make([]byte, 4+24*len(qs))
+	}
+	// qbuf = n x {u32 slen; u32 elen; u64 rev; i64 limit (ignored); start; end}
+	qbuf := make([]byte, 0, 64*len(qs)+1)
+	for _, q := range qs {
+		var h [24]byte
+		binary.LittleEndian.PutUint32(h[0:], uint32(len(q.Key)))
+		binary.LittleEndian.PutUint32(h[4:], uint32(len(q.End)))
+		binary.LittleEndian.PutUint64(h[8:], q.Revision)
+		qbuf = append(qbuf, h[:]...)
+		qbuf = append(qbuf, q.Key...)
+		qbuf = append(qbuf, q.End...)
+	}
+	qbuf = append(qbuf, 0) // never a nil pointer, even for zero queries
+	for {
+		var outLen C.size_t
+		var total C.ulonglong
+		rc := C.kb_count_batch(b.h, bptr(qbuf), C.size_t(len(qs)), 0,
+			bptr(buf), C.size_t(len(buf)), &outLen, &total)
+		if rc == C.KB_ENOBUF { // nothing written; out_len carries need
+			buf = make([]byte, int(outLen))
+			continue
+		}
+		if rc != C.KB_OK {
+			return nil, buf, statusToErr(rc)
+		}
+		// reply = u32 n; n x {i32 status; i32 0; u64 header_rev; u64 count}
+		n := int(binary.LittleEndian.Uint32(buf))
+		out := make([]CountResult, 0, n)
+		for i := 0; i < n; i++ {
+			d := buf[4+24*i:]
+			st := C.int(int32(binary.LittleEndian.Uint32(d)))
+			if st != C.KB_OK {
+				out = append(out, CountResult{Err: statusToErr(st)})
+				continue
+			}
+			out = append(out, CountResult{Resp: &proto.CountResponse{
+				Header: header(binary.LittleEndian.Uint64(d[8:])),
+				Count:  binary.LittleEndian.Uint64(d[16:])}})
+		}
+		return out, buf, nil
+	}
+}
+
 func (b *amdBackend) Compact(ctx context.Context, revision uint64) (*proto.CompactResponse, error) {
 	var outRev C.uint64_t
 	rc := C.kb_compact(b.h, C.uint64_t(revision), &outRev)

@@ -22,7 +22,7 @@ def build(force: bool = False) -> str:
     srcs = [os.path.join(src_dir, f) for f in ("slab.hip", "store.cc", "cabi.cc",
                                                "comm.cc", "slab_dev.h", "store.h",
                                                "wpoll.h", "lplan.h", "gplan.h",
-                                               "stepstage.h", "dmerge.h")]
+                                               "stepstage.h", "dmerge.h", "cplan.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "kb_slab.h"))
     stale = force or not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -260,6 +260,36 @@ class Store:
                               C.c_size_t(len(end)), C.byref(hr), C.byref(cnt))
         return rc, hr.value, cnt.value
 
+    def count_batch(self, queries):
+        """Many Counts in one call (kb_count_batch; product ABI only). queries
+        = [(start, end, rev, limit), ...] as for list_batch (limit is ignored,
+        rev 0 = latest). Returns (rc, [(status, header_rev, count), ...],
+        raw_reply) in query order. KB_ENOBUF is handled here by growing the
+        buffer and repeating the call (the failed attempt wrote nothing)."""
+        n = len(queries)
+        qbuf = self.encode_queries(queries)
+        out_len = C.c_size_t(); total = C.c_ulonglong()
+        f = self._f("count_batch")
+        buf, cap = self.buf, self.BUF
+        for _ in range(4):
+            rc = f(C.c_void_p(self.h), qbuf, C.c_size_t(n), C.c_int(0), buf,
+                   C.c_size_t(cap), C.byref(out_len), C.byref(total))
+            if rc != ENOBUF:
+                break
+            cap = out_len.value
+            buf = C.create_string_buffer(cap)
+        if rc != OK:
+            return rc, [], b""
+        raw = C.string_at(buf, out_len.value)
+        (cnt,) = struct.unpack_from("<I", raw, 0)
+        assert cnt == n and len(raw) == 4 + 24 * n, (cnt, n, len(raw))
+        res = []
+        for i in range(n):
+            st, _z, hr, c = struct.unpack_from("<iiQQ", raw, 4 + 24 * i)
+            res.append((st, hr, c))
+        assert sum(c for _, _, c in res) == total.value
+        return rc, res, raw
+
     def compact(self, rev: int = 0):
         out = C.c_uint64()
         rc = self._f("compact")(C.c_void_p(self.h), C.c_uint64(rev), C.byref(out))

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/kb_slab.h"
+#include "cplan.h"
 #include "store.h"
 
 using kbstore::Bytes;
@@ -267,6 +268,45 @@ int kb_count(kb_store* h, const uint8_t* start, size_t slen, const uint8_t* end,
   *header_rev = r.header_revision;
   *count = r.count;
   return st;
+}
+
+int kb_count_batch(kb_store* h, const uint8_t* qbuf, size_t n, int flags,
+                   uint8_t* out, size_t cap, size_t* out_len,
+                   unsigned long long* total_count) {
+  std::string err;
+  size_t len = 0;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->CountBatch(qbuf, n, flags, out, cap, &len, &total,
+                                      &err);
+  if (out_len) *out_len = len;
+  if (total_count) *total_count = total;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
+int kb_test_count_plan(const long long* bounds, size_t nq, long long tile,
+                       unsigned long long* pfx, int* t_query, int* t_run,
+                       long long* t_r0, long long* t_r1, size_t tile_cap,
+                       size_t* n_tiles) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "bound width");
+  if (tile < kbcount::kMinTile || tile != kbcount::ClampTile(tile) ||
+      nq > 0x3fffffffull)
+    return KB_EINVALID;
+  const int64_t* b = (const int64_t*)bounds;
+  std::vector<uint64_t> px(2 * nq + 1);
+  const uint64_t total = kbcount::BuildPrefix(b, (int)nq, tile, px.data());
+  for (size_t s = 0; s <= 2 * nq && pfx; ++s) pfx[s] = px[s];
+  if (n_tiles) *n_tiles = (size_t)total;
+  if (total > tile_cap) return KB_ENOBUF;
+  for (uint64_t t = 0; t < total; ++t) {
+    const kbcount::Tile tl = kbcount::MapTile(b, px.data(), (int)(2 * nq), t, tile);
+    if (t_query) t_query[t] = tl.query;
+    if (t_run) t_run[t] = tl.run;
+    if (t_r0) t_r0[t] = tl.r0;
+    if (t_r1) t_r1[t] = tl.r1;
+  }
+  return KB_OK;
 }
 
 int kb_compact(kb_store* h, uint64_t rev, uint64_t* out_rev) {

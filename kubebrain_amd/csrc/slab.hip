@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "cplan.h"
 #include "dmerge.h"
 #include "slab_dev.h"
 #include "stepstage.h"
@@ -1833,6 +1834,127 @@ __global__ __launch_bounds__(256) void k_get_emit(
   }
 }
 
+// ---- batched Count (kb_count_batch) --------------------------
+// Counting needs no order: the winner predicate is a pure function of row i,
+// row i + 1, the shadow column and R. k_range_bounds (unchanged) resolves the
+// four run bounds per query, k_count_plan numbers the T-row tiles of the
+// launch's 2 * nq segments (cplan.h), k_count_tiles spreads the tiles over the
+// chip and adds each tile's winners into its query's counter. k_range_scan2
+// and scan_run_winners are not involved.
+//
+// chdr = {u64 tiles done; u64 rows done; u64 tiles planned; u64 rows planned;
+// nq x u64 count}: the block the host reads back.
+constexpr int COUNT_HDR = 4;
+
+// one 256-thread block per launch, 256 segments per pass: tiles per segment
+// and their exclusive scan (wave scans chained through LDS) into pfx[2 * nq
+// + 1]; the planned totals; the counters k_count_tiles adds to are zeroed
+// here, one launch ahead of their first increment.
+__global__ __launch_bounds__(256) void k_count_plan(
+    const int64_t* __restrict__ bounds, int nq, int64_t T,
+    uint64_t* __restrict__ pfx, uint64_t* __restrict__ chdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nseg = 2 * nq;
+  __shared__ uint64_t wsum[4], wrows[4];
+  uint64_t base = 0, rows_all = 0;  // block-uniform running totals
+  for (int c0 = 0; c0 < nseg; c0 += 256) {
+    const int s = c0 + threadIdx.x;
+    uint64_t tiles = 0, rows = 0;
+    if (s < nseg) {
+      const int64_t lo = kbcount::SegLo(bounds, s), hi = kbcount::SegHi(bounds, s);
+      tiles = kbcount::SegTiles(lo, hi, T);
+      rows = (uint64_t)kbcount::SegRows(lo, hi);
+    }
+    const uint64_t incl = wp_scan64(tiles, lane);
+    const uint64_t rincl = wp_scan64(rows, lane);
+    if (lane == 63) { wsum[w] = incl; wrows[w] = rincl; }
+    __syncthreads();
+    uint64_t woff = 0, tot = 0, rtot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < w) woff += wsum[k];
+      tot += wsum[k];
+      rtot += wrows[k];
+    }
+    if (s < nseg) pfx[s] = base + woff + incl - tiles;
+    base += tot;
+    rows_all += rtot;
+    __syncthreads();  // wsum / wrows reused by the next pass
+  }
+  for (int q = threadIdx.x; q < nq; q += 256) chdr[COUNT_HDR + q] = 0;
+  if (threadIdx.x == 0) {
+    pfx[nseg] = base;
+    chdr[0] = 0;
+    chdr[1] = 0;
+    chdr[2] = base;
+    chdr[3] = rows_all;
+  }
+}
+
+// fixed grid (sized by the CU count: the tile total is known only on the
+// device), blocks grid-stride over tile ids. A block maps its tile through
+// cplan.h, its 4 waves take the 64-row slices of [r0, r1) round-robin: rev /
+// meta / shadow 8-byte streams, no key bytes. The rev[i + 1] load is guarded
+// by the end of the SEGMENT, not of the tile: the last row of a tile looks
+// into the next tile. The shadow column applies to the base run only and
+// only while the delta holds rows, as in scan_run_winners. Per tile: ballot
+// + popcount per wave, a block reduction through LDS, ONE 64-bit atomicAdd
+// into the query's counter (integer adds commute: exact in any order). A tile
+// whose rows leave its run is skipped and not counted as done, which the
+// host reports as an error.
+__global__ __launch_bounds__(256) void k_count_tiles(
+    Run b, int64_t n, Run d, int64_t dn, const uint64_t* __restrict__ shadow,
+    const DevRangeQ* __restrict__ qs, int nq,
+    const int64_t* __restrict__ bounds, const uint64_t* __restrict__ pfx,
+    int64_t T, uint64_t* __restrict__ chdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nseg = 2 * nq;
+  __shared__ uint32_t wcnt[4];
+  const uint64_t total = pfx[nseg];
+  uint64_t done = 0, rows_done = 0;  // thread 0's tallies of this block
+  for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {
+    const kbcount::Tile tl = kbcount::MapTile(bounds, pfx, nseg, t, T);
+    const bool isd = tl.run != 0;
+    const int64_t run_n = isd ? dn : n;
+    if (tl.r0 < 0 || tl.r0 >= tl.r1 || tl.r1 > tl.hi || tl.hi > run_n)
+      continue;  // block-uniform
+    const uint64_t* __restrict__ rev = isd ? d.rev : b.rev;
+    const uint64_t* __restrict__ meta = isd ? d.meta : b.meta;
+    const uint64_t* __restrict__ sh = (!isd && dn > 0) ? shadow : nullptr;
+    const uint64_t R = qs[tl.query].read_rev;
+    const int64_t seg_hi = tl.hi;
+    uint32_t cnt = 0;  // wave-uniform
+#pragma unroll 4
+    for (int64_t i0 = tl.r0 + ((int64_t)w << 6); i0 < tl.r1; i0 += 256) {
+      const int64_t i = i0 + lane;
+      bool win = false;
+      if (i < tl.r1) {
+        const uint64_t rv = rev[i], m = meta[i];
+        const uint64_t rvn = (i + 1 < seg_hi) ? rev[i + 1] : 0;
+        const uint64_t s = sh ? sh[i] : UINT64_MAX;
+        if (rv > 0 && rv <= R && !(m & M_TOMB) && !(s != UINT64_MAX && s <= R))
+          win = !(m & M_SAME_NEXT) || rvn > R;
+      }
+      cnt += (uint32_t)__popcll(__ballot(win));
+    }
+    if (lane == 0) wcnt[w] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint64_t c = (uint64_t)wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+      if (c)
+        atomicAdd((unsigned long long*)&chdr[COUNT_HDR + tl.query],
+                  (unsigned long long)c);
+      done += 1;
+      rows_done += (uint64_t)(tl.r1 - tl.r0);
+    }
+    __syncthreads();  // wcnt reused by the next tile
+  }
+  if (threadIdx.x == 0 && done) {
+    atomicAdd((unsigned long long*)&chdr[0], (unsigned long long)done);
+    atomicAdd((unsigned long long*)&chdr[1], (unsigned long long)rows_done);
+  }
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -2106,6 +2228,53 @@ struct Slab::Impl {
     return true;
   }
 
+  // batched Count (allocated on first use). Nothing here is shared with the
+  // range batch: queries, key tails, bounds and the two counters
+  // k_range_bounds zeroes are the call's own, so what LastRangeWire and a
+  // later RangeBatchFinish read stays as it was.
+  int64_t count_tile = kbcount::kDefaultTile;  // KB_COUNT_TILE
+  int count_grid = 2048;                       // CUs x 8 blocks
+  DevRangeQ *d_cq = nullptr, *h_cq = nullptr;
+  uint8_t* d_ctails = nullptr;
+  int64_t ctails_cap = 0;
+  int64_t* d_cbounds = nullptr;             // [4 * max_q]
+  uint64_t* d_cpfx = nullptr;               // [2 * max_q + 1]
+  uint64_t *d_chdr = nullptr, *h_chdr = nullptr;  // [COUNT_HDR + max_q]
+  unsigned long long* d_cctr = nullptr;     // [2] k_range_bounds' counter pair
+  hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr, ev_c2 = nullptr;
+  void free_count() {
+    for (void* q : {(void*)d_cq, (void*)d_ctails, (void*)d_cbounds,
+                    (void*)d_cpfx, (void*)d_chdr, (void*)d_cctr})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_cq, (void*)h_chdr})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_c0, ev_c1, ev_c2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_count(int64_t tail_bytes, std::string* err) {
+    if (!d_chdr) {
+      HIP_CHECK(hipEventCreate(&ev_c0));
+      HIP_CHECK(hipEventCreate(&ev_c1));
+      HIP_CHECK(hipEventCreate(&ev_c2));
+      HIP_CHECK(hipHostMalloc(&h_cq, (int64_t)max_q * sizeof(DevRangeQ)));
+      HIP_CHECK(hipHostMalloc(&h_chdr, (int64_t)(COUNT_HDR + max_q) * 8));
+      HIP_CHECK(hipMalloc(&d_cq, (int64_t)max_q * sizeof(DevRangeQ)));
+      HIP_CHECK(hipMalloc(&d_cbounds, (int64_t)max_q * 4 * 8));
+      HIP_CHECK(hipMalloc(&d_cpfx, (int64_t)(2 * max_q + 1) * 8));
+      HIP_CHECK(hipMalloc(&d_cctr, 16));
+      HIP_CHECK(hipMalloc(&d_chdr, (int64_t)(COUNT_HDR + max_q) * 8));
+    }
+    if (tail_bytes > ctails_cap || !d_ctails) {
+      if (d_ctails) (void)hipFree(d_ctails);
+      d_ctails = nullptr;
+      ctails_cap = 0;
+      int64_t cap = tail_bytes * 2 + 4096;
+      HIP_CHECK(hipMalloc(&d_ctails, cap));
+      ctails_cap = cap;
+    }
+    return true;
+  }
+
   // KB_SCAN_DBG=1: per-phase wall_clock64 cycle sums from k_range_scan2
   // ([0]=bounds [1]=pass1a [2]=pass1b [3]=scatter [4]=merge [5]=block total)
   unsigned long long* d_dbg = nullptr;
@@ -2225,6 +2394,7 @@ struct Slab::Impl {
     free_wpoll();
     free_list();
     free_getb();
+    free_count();
     if (h_pack) (void)hipHostFree(h_pack);
     for (int i = 0; i < 2; ++i) {
       if (h_resmeta[i]) (void)hipHostFree(h_resmeta[i]);
@@ -2477,6 +2647,13 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   I->scan_t &= ~63;
   I->max_cap = env_i64("KB_MAX_CAP", 4352);
   I->arena_bytes = env_i64("KB_ARENA_BYTES", 384ll << 20);
+  I->count_tile = kbcount::ClampTile(env_i64("KB_COUNT_TILE", kbcount::kDefaultTile));
+  {
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                I->device);
+    I->count_grid = (cus > 0 ? cus : 256) * 8;
+  }
   std::string lerr;
   if (!err) err = &lerr;
   auto fail = [&](const char*) { delete s; return (Slab*)nullptr; };
@@ -3329,6 +3506,64 @@ bool Slab::GetBatchLaunch(const DevGetQ* qs, int nq, const std::string& qtails,
   perf.get_batch_launches++;
   I->get_nq = nq;
   *hdr = (const GetBatchHdr*)I->h_ghdr;
+  return true;
+}
+
+// ---- batched Count (kb_count_batch) ---------------------------------------
+
+int64_t Slab::count_tile() const { return p->count_tile; }
+
+bool Slab::CountBatchLaunch(const DevRangeQ* qs, int nq,
+                            const std::string& qtails,
+                            const CountBatchHdr** hdr, std::string* err) {
+  Impl* I = p;
+  static_assert(sizeof(CountBatchHdr) == (COUNT_HDR + 1) * 8, "count header");
+  if (nq <= 0 || nq > I->max_q) {
+    if (err) *err = "count batch: bad sub-batch size (KB_MAX_Q)";
+    return false;
+  }
+  if (!I->ensure_count((int64_t)qtails.size(), err)) return false;
+  memcpy(I->h_cq, qs, sizeof(DevRangeQ) * (size_t)nq);
+  HIP_CHECK(hipMemcpyAsync(I->d_cq, I->h_cq, sizeof(DevRangeQ) * (size_t)nq,
+                           hipMemcpyHostToDevice, I->stream));
+  if (!qtails.empty())
+    HIP_CHECK(hipMemcpyAsync(I->d_ctails, qtails.data(), qtails.size(),
+                             hipMemcpyHostToDevice, I->stream));
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  hipLaunchKernelGGL(k_range_bounds, dim3(nq), dim3(256), 0, I->stream,
+                     I->A.run(), I->n, I->DA.run(), I->dn, I->spillA,
+                     I->d_ctails, I->d_cq, nq, I->d_cbounds, I->d_cctr);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_c0, I->stream));
+  hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(256), 0, I->stream,
+                     I->d_cbounds, nq, I->count_tile, I->d_cpfx, I->d_chdr);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_count_tiles, dim3((uint32_t)I->count_grid), dim3(256), 0,
+                     I->stream, I->A.run(), I->n, I->DA.run(), I->dn, I->shadow,
+                     I->d_cq, nq, I->d_cbounds, I->d_cpfx, I->count_tile,
+                     I->d_chdr);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_c1, I->stream));
+  // the one small readback: four totals and 8 B per query
+  HIP_CHECK(hipMemcpyAsync(I->h_chdr, I->d_chdr, (int64_t)(COUNT_HDR + nq) * 8,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_c2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_c0, I->ev_c1);
+  perf.count_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_c1, I->ev_c2);
+  perf.count_d2h_ms += ms;
+  const CountBatchHdr* h = (const CountBatchHdr*)I->h_chdr;
+  if (h->tiles != h->tiles_planned || h->rows != h->rows_planned) {
+    if (err) *err = "count batch: the tile kernel did not cover the plan";
+    return false;
+  }
+  perf.count_batch_launches++;
+  perf.count_batch_tiles += (int64_t)h->tiles;
+  perf.count_batch_rows += (int64_t)h->rows;
+  *hdr = h;
   return true;
 }
 

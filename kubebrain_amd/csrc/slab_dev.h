@@ -134,6 +134,12 @@ struct Perf {
   double get_batch_ms = 0, get_batch_d2h_ms = 0;
   int64_t get_batch_calls = 0, get_batch_q_dev = 0, get_batch_q_host = 0,
           get_batch_found = 0, get_batch_bytes = 0, get_batch_launches = 0;
+  // batched Count (kb_count_batch): k_count_plan + k_count_tiles kernel time,
+  // the counter D2H, queries the kernels served, launches, tiles counted and
+  // rows covered by them (= sum of the segment lengths)
+  double count_ms = 0, count_d2h_ms = 0;
+  int64_t count_batch_calls = 0, count_batch_q = 0, count_batch_launches = 0,
+          count_batch_tiles = 0, count_batch_rows = 0;
   // which mergeRuns branch ran (k_merge_small / k_delta_rank + k_delta_scatter /
   // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
   // async no-sync branch, and delta->base folds: the tests prove with these
@@ -183,6 +189,13 @@ struct GetBatchHdr {
 };
 static_assert(sizeof(GetDirEntry) == 32, "get directory entry layout");
 static_assert(sizeof(GetBatchHdr) == 48, "get launch header layout");
+// batched Count (kb_count_batch): what k_count_plan and k_count_tiles leave
+// per launch. tiles / rows are what the tile kernel covered, *_planned what
+// the plan kernel derived from the bounds; they must agree.
+struct CountBatchHdr {
+  uint64_t tiles, rows, tiles_planned, rows_planned;
+  uint64_t count[1];  // nq entries
+};
 
 
 
@@ -342,6 +355,16 @@ class Slab {
   bool GetBatchHostValue(const DevGetQ& q, const std::string& qtails,
                          uint64_t mod_rev, uint64_t vlen, uint8_t* dst,
                          std::string* err);
+
+  // batched Count (kb_count_batch). CountBatchLaunch uploads
+  // nq <= KB_MAX_Q queries (read_rev resolved; start_rev, cap and the flags
+  // are not read) and runs k_range_bounds, k_count_plan and k_count_tiles
+  // back to back on buffers of its own, then reads back the totals and 8 B
+  // per query; *hdr points into pinned memory valid until the next call.
+  // Writes neither the winner tables nor the arena nor the range counters.
+  bool CountBatchLaunch(const DevRangeQ* qs, int nq, const std::string& qtails,
+                        const CountBatchHdr** hdr, std::string* err);
+  int64_t count_tile() const;  // KB_COUNT_TILE: rows per tile
 
   // compaction mark+sweep over encoded borders (compact.go:55-68 +
   // scanner.go:444-491, 566-591). Bounds are (key96, rev) pairs.

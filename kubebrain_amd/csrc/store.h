@@ -89,6 +89,14 @@ class Store {
                   size_t cap, size_t* out_len, uint64_t* total_found,
                   std::string* err = nullptr);
   CountResponse Count(const Bytes& start, const Bytes& end, Status* st);
+  // batched Count (kb_count_batch): n Counts under one mutex hold, each range
+  // cut into row tiles counted across the chip; qbuf = the
+  // kb_bench_range query blob (limit ignored, rev 0 = latest), reply = u32 n;
+  // n x {i32 status; i32 0; u64 header_rev; u64 count}. NOBUF writes nothing
+  // (*out_len = required size).
+  Status CountBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                    size_t cap, size_t* out_len, uint64_t* total_count,
+                    std::string* err = nullptr);
   uint64_t Compact(uint64_t revision, Status* st);
   uint64_t GetCurrentRevision();
   void SetCurrentRevision(uint64_t rev);
