@@ -250,6 +250,41 @@ int kb_watch_poll(kb_store*, long long wid, uint8_t* out, size_t cap, size_t* ou
 int kb_watch_poll_batch(kb_store*, const long long* wids, size_t n,
                         uint8_t* out, size_t cap, size_t* out_len,
                         unsigned long long* total_events);
+/* Register n watchers in one call (watch.go:37-99 per watcher; Ring.FindEvents,
+ * ring.go:84-118 for the catch-up), one mutex hold, one event pump.
+ * wbuf = n x {u32 plen; u64 rev; prefix} in wbuf_len bytes — the blob shape of
+ * kb_get_batch with the watch prefix in place of the key. wids[i] and
+ * statuses[i] are EXACTLY what n calls kb_watch(prefix_i, plen_i, rev_i,
+ * &status) made in that order at that moment would have returned: per-entry
+ * status KB_OK, KB_EWATCH_LOW, KB_EWATCH_EMPTY or KB_EINTERNAL, a failed
+ * entry has wids[i] = -1 and takes neither a watcher id nor a device slot,
+ * and one failed entry never fails the call. Each new watcher queues exactly
+ * the catch-up events kb_watch would have queued (the same 512-event refs
+ * from its own first ring sequence on, so slow-consumer drops happen at the
+ * same moment) and its from_rev follows watch.go:91-95: newest revision + 1
+ * if the catch-up found anything, else rev. *total_pending = catch-up events
+ * queued across the batch. A prefix may repeat in a batch.
+ * flags must be 0, else KB_EINVALID. n == 0 is valid. A blob whose bytes run
+ * out before entry n - 1 ends (wbuf_len too small) is KB_EINVALID and
+ * registers nothing. May be interleaved freely with kb_watch, kb_watch_poll,
+ * kb_watch_poll_batch, kb_watch_cancel and writes; a pending pipelined
+ * kb_bench_step batch is collected first.
+ * The catch-up bits of all watchers, their refs and their device filter rows
+ * are produced by HIP kernels that stage the resident event ring through LDS
+ * once per 64 watchers; the dense bitmap scratch is bounded
+ * by KB_WATCH_REG_BYTES (default 64 MiB), a larger batch is served in
+ * sub-batches inside the call. A prefix longer than 96 B takes exact bits
+ * computed by the host, as in kb_watch. */
+int kb_watch_batch(kb_store*, const uint8_t* wbuf, size_t wbuf_len, size_t n,
+                   int flags, long long* wids, int* statuses,
+                   unsigned long long* total_pending);
+/* TEST-ONLY: the pending delivery refs of a watcher, as kb_watch /
+ * kb_watch_batch / the fan-out queued them. out = u32 nrefs; u64 from_rev;
+ * i64 pend_events; nrefs x {i64 base; i32 count; i32 0; u64 words[8]}.
+ * KB_ENOBUF with *out_len = needed size when cap is too small;
+ * KB_EWATCH_DROPPED for an unknown wid. Launches nothing, changes nothing. */
+int kb_test_watch_refs(kb_store*, long long wid, uint8_t* out, size_t cap,
+                       size_t* out_len);
 void kb_watch_cancel(kb_store*, long long wid);
 
 /* ---- streaming full-range reads (backend.ListByStream range.go:247-256 +

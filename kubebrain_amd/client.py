@@ -346,6 +346,30 @@ class Store:
         assert sum(len(e) for _, e in res) == total.value
         return rc, res, sections
 
+    @staticmethod
+    def encode_watches(watches) -> bytes:
+        """The blob of kb_watch_batch: per watcher (prefix, rev) ->
+        {u32 plen; u64 rev; prefix}. A bare prefix means rev 0."""
+        ws = [(w, 0) if isinstance(w, (bytes, bytearray)) else w for w in watches]
+        return b"".join(struct.pack("<IQ", len(p), rev) + p for p, rev in ws)
+
+    def watch_batch(self, watches):
+        """Register many watchers in one call (kb_watch_batch; product ABI
+        only). watches = [(prefix, rev), ...] (or bare prefixes, rev 0).
+        Returns (rc, [(status, wid), ...], total_pending) in entry order: per
+        entry what watch(prefix, rev) returns, wid -1 for a failed entry."""
+        n = len(watches)
+        wbuf = self.encode_watches(watches)
+        wids = (C.c_longlong * max(n, 1))()
+        sts = (C.c_int * max(n, 1))()
+        total = C.c_ulonglong()
+        rc = self._f("watch_batch")(C.c_void_p(self.h), wbuf,
+                                    C.c_size_t(len(wbuf)), C.c_size_t(n),
+                                    C.c_int(0), wids, sts, C.byref(total))
+        if rc != OK:
+            return rc, [], 0
+        return rc, [(sts[i], wids[i]) for i in range(n)], total.value
+
     def watch_cancel(self, wid: int):
         self._f("watch_cancel")(C.c_void_p(self.h), C.c_longlong(wid))
 

@@ -375,6 +375,32 @@ int kb_test_wpoll_plan(const unsigned long long* ref_bytes,
   return rc;
 }
 
+int kb_watch_batch(kb_store* h, const uint8_t* wbuf, size_t wbuf_len, size_t n,
+                   int flags, long long* wids, int* statuses,
+                   unsigned long long* total_pending) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "wid width");
+  static_assert(sizeof(int) == sizeof(int32_t), "status width");
+  std::string err;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->WatchBatch(wbuf, wbuf_len, n, flags, (int64_t*)wids,
+                                      (int32_t*)statuses, &total, &err);
+  if (total_pending) *total_pending = total;
+  for (size_t i = 0; st == kbstore::OK && i < n; ++i)
+    if (statuses[i] == kbstore::INTERNAL) { set_err(KB_EINTERNAL, err); break; }
+  return st;
+}
+
+int kb_test_watch_refs(kb_store* h, long long wid, uint8_t* out, size_t cap,
+                       size_t* out_len) {
+  std::string wire;
+  Status st = ((Store*)h)->TestWatchRefs(wid, &wire);
+  if (st != kbstore::OK) return st;
+  *out_len = wire.size();
+  if (wire.size() > cap) return KB_ENOBUF;
+  memcpy(out, wire.data(), wire.size());
+  return KB_OK;
+}
+
 void kb_watch_cancel(kb_store* h, long long wid) { ((Store*)h)->WatchCancel(wid); }
 
 long long kb_stream_open(kb_store* h, const uint8_t* start, size_t slen,

@@ -15,6 +15,7 @@
 #include "dmerge.h"
 #include "slab_dev.h"
 #include "stepstage.h"
+#include "wreg.h"
 
 namespace kbslab {
 
@@ -1955,6 +1956,308 @@ __global__ __launch_bounds__(256) void k_count_tiles(
   }
 }
 
+// ---- batched watch registration: catch-up for many watchers --------------
+// (kb_watch_batch; watch.go:37-99 + Ring.FindEvents,
+// ring.go:84-118 per watcher). k_watch_catchup re-reads the ring span once
+// per watcher; here a block stages each 64-event chunk of the resident ring
+// through LDS once and tests a 64-watcher slice against it, on ONE global
+// chunk grid anchored at the oldest resident sequence S (wreg.h). k_wreg_plan
+// then finds every watcher's own first sequence lo, counts its non-empty
+// 512-event refs through the funnel of wreg.h, commits the watcher table rows
+// and lays the refs of the sub-batch out back to back; k_wreg_emit writes
+// them in the {base, count, words[8]} form kb_watch builds.
+
+constexpr int WREG_RUN = 16;  // chunks per scan block: 4 waves x 4 rounds
+
+// chunk g of the global grid -> registers: the 64 x 96 B key columns as 384
+// 16-byte vectors, six per lane, consecutive lanes on consecutive vectors
+// (every ring slot is 16-byte aligned: KEYW = 6 x 16), plus one revision per
+// lane. Ring slots wrap, so the slot is derived per element from the chunk's
+// first slot.
+__device__ __forceinline__ void wreg_load_chunk(
+    const uint8_t* __restrict__ er_keys, const uint64_t* __restrict__ er_rev,
+    int64_t ring_cap, int64_t S, int64_t N, int64_t g, int64_t gwords, int lane,
+    uint4 (&kv)[6], uint64_t& rv) {
+  if (g >= gwords) return;  // wave-uniform
+  const int64_t seq0 = g << 6;
+  const int cn = (int)min((int64_t)64, N - seq0);
+  const int64_t slot0 = (S + seq0) % ring_cap;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const int v = i * 64 + lane, j = v / 6, k = v - j * 6;
+    uint4 t = make_uint4(0, 0, 0, 0);
+    if (j < cn) {
+      int64_t slot = slot0 + j;
+      if (slot >= ring_cap) slot -= ring_cap;
+      t = ((const uint4*)(er_keys + slot * KEYW))[k];
+    }
+    kv[i] = t;
+  }
+  rv = 0;
+  if (lane < cn) {
+    int64_t slot = slot0 + lane;
+    if (slot >= ring_cap) slot -= ring_cap;
+    rv = er_rev[slot];
+  }
+}
+
+// registers -> one wave's LDS buffer, the same element guards as the load
+__device__ __forceinline__ void wreg_stash_chunk(
+    uint4* __restrict__ lk, uint64_t* __restrict__ lr, int64_t N, int64_t g,
+    int64_t gwords, int lane, const uint4 (&kv)[6], uint64_t rv) {
+  if (g >= gwords) return;  // wave-uniform
+  const int cn = (int)min((int64_t)64, N - (g << 6));
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const int v = i * 64 + lane;
+    if (v / 6 < cn) lk[v] = kv[i];
+  }
+  if (lane < cn) lr[lane] = rv;
+}
+
+// grid = (64-watcher slices, runs of WREG_RUN chunks), 256 threads. Lane =
+// watcher: its prefix stays in 12 registers, its four waves take four chunks
+// of the run per round. Staging is double buffered through registers: the
+// next round's chunk is requested from HBM before the current one is tested
+// out of LDS and lands in the other LDS buffer after the test. All lanes of
+// a wave read the same staged event, so the LDS reads are broadcasts. The
+// words of a run are transposed through LDS, so a watcher's WREG_RUN words
+// leave as one contiguous 128 B store into scratch[watcher][gword].
+// The predicate is k_watch_filter2's: er_rev >= rev and the first min(plen,
+// 96) bytes equal. A block whose newest event is older than every revision
+// of its slice holds no bit for anyone and exits before staging; those words
+// lie below each watcher's lo and are never read (wreg.h G0).
+__global__ __launch_bounds__(256) void k_wreg_scan(
+    const uint8_t* __restrict__ er_keys, const uint64_t* __restrict__ er_rev,
+    int64_t ring_cap, int64_t S, int64_t N, const WregEntry* __restrict__ ent,
+    int nw, uint64_t* __restrict__ scratch, int64_t gwords) {
+  __shared__ uint4 lkeys[4][2][64 * 6];
+  __shared__ uint64_t lrev[4][2][64];
+  __shared__ uint64_t tile[64][WREG_RUN + 1];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int w = blockIdx.x * 64 + lane;
+  const int64_t run0 = (int64_t)blockIdx.y * WREG_RUN;
+  if (run0 >= gwords) return;
+  const bool act = w < nw && (ent[w].flags & WREG_SCAN);
+  const uint64_t rev = act ? ent[w].rev : UINT64_MAX;
+  uint64_t mn = rev;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint64_t o = wp_shfl64(mn, lane ^ d);
+    mn = o < mn ? o : mn;
+  }
+  {
+    const int64_t last = min(N, (run0 + WREG_RUN) << 6) - 1;
+    if (er_rev[(S + last) % ring_cap] < mn) return;  // block-uniform
+  }
+  uint64_t pf[KEYW / 8];
+  uint32_t plen = 0;
+#pragma unroll
+  for (int k = 0; k < KEYW / 8; ++k)
+    pf[k] = act ? ((const uint64_t*)ent[w].pfx)[k] : 0;
+  if (act) plen = min(ent[w].plen, (uint32_t)KEYW);
+  const int nwd = (int)((plen + 7) >> 3);  // key words the prefix reaches
+  const uint64_t lastmask =
+      (plen & 7) ? ((1ull << (8 * (plen & 7))) - 1) : ~0ull;
+  int maxnw = nwd;  // wave-uniform bound: no LDS read for words nobody needs
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) maxnw = max(maxnw, __shfl_xor(maxnw, d, 64));
+
+  uint4 kv[6] = {};
+  uint64_t rv = 0;
+  wreg_load_chunk(er_keys, er_rev, ring_cap, S, N, run0 + wv, gwords, lane, kv, rv);
+  wreg_stash_chunk(lkeys[wv][0], lrev[wv][0], N, run0 + wv, gwords, lane, kv, rv);
+  __syncthreads();
+  for (int it = 0; it < WREG_RUN / 4; ++it) {
+    const int b = it & 1;
+    const int64_t g = run0 + it * 4 + wv;
+    const int64_t gn = g + 4;
+    if (it + 1 < WREG_RUN / 4)
+      wreg_load_chunk(er_keys, er_rev, ring_cap, S, N, gn, gwords, lane, kv, rv);
+    uint64_t acc = 0;
+    if (g < gwords) {
+      const int cn = (int)min((int64_t)64, N - (g << 6));
+      const uint64_t* kb = (const uint64_t*)lkeys[wv][b];
+      for (int j = 0; j < cn; ++j) {
+        uint64_t diff = 0;
+#pragma unroll
+        for (int k = 0; k < KEYW / 8; ++k) {
+          if (k < maxnw) {  // wave-uniform
+            uint64_t x = kb[j * (KEYW / 8) + k] ^ pf[k];
+            if (k == nwd - 1) x &= lastmask;
+            if (k >= nwd) x = 0;
+            diff |= x;
+          }
+        }
+        const bool ok = act && lrev[wv][b][j] >= rev && diff == 0;
+        acc |= (uint64_t)ok << j;
+      }
+    }
+    tile[lane][it * 4 + wv] = acc;
+    if (it + 1 < WREG_RUN / 4)
+      wreg_stash_chunk(lkeys[wv][b ^ 1], lrev[wv][b ^ 1], N, gn, gwords, lane, kv, rv);
+    __syncthreads();
+  }
+  for (int idx = threadIdx.x; idx < 64 * WREG_RUN; idx += 256) {
+    const int wl = idx / WREG_RUN, k = idx % WREG_RUN;
+    const int64_t ww = (int64_t)blockIdx.x * 64 + wl, g = run0 + k;
+    if (ww < nw && g < gwords) scratch[ww * gwords + g] = tile[wl][k];
+  }
+}
+
+// one wave per watcher, four per block, the whole chip. A WREG_SCAN watcher
+// finds its lo by lower bound over er_rev in ring order (revisions ascend),
+// then walks its own words 64 at a time: lane l holds own word i0 + l, a
+// ballot of the non-zero ones gives the non-empty refs of the round (a ref
+// = 8 consecutive lanes = one byte of the ballot) and a wave sum the events.
+// from_rev follows watch.go:91-95. Every watcher, scanned or not, has its
+// table row committed here from the uploaded entry. The block that arrives
+// last (a ticket after a device-wide fence) makes the exclusive scan of the
+// ref counts, 256 watchers per pass, wave scans chained through LDS as in
+// k_get_plan, and leaves the ticket at zero for the next launch.
+// hdr = {u64 total_refs; u64 total_pending; nw x {u32 nrefs; u32 0; u64
+// from_rev; u64 pend_events; u64 ref_off}}.
+__global__ __launch_bounds__(256) void k_wreg_plan(
+    const uint64_t* __restrict__ er_rev, int64_t ring_cap, int64_t S, int64_t N,
+    uint64_t newest_rev, const WregEntry* __restrict__ ent, int nw,
+    const uint64_t* __restrict__ scratch, int64_t gwords,
+    uint8_t* __restrict__ wpfx, uint32_t* __restrict__ wplen,
+    uint64_t* __restrict__ wfrom, uint32_t* __restrict__ wlive, int64_t wcap,
+    int64_t* __restrict__ wlo, uint64_t* hdr, unsigned int* ticket) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int w = blockIdx.x * 4 + wv;
+  if (w < nw) {  // wave-uniform
+    const WregEntry& e = ent[w];
+    uint64_t from = e.rev, pend = 0;
+    uint32_t nrefs = 0;
+    int64_t lo = S + N;
+    if (e.flags & WREG_SCAN) {
+      int64_t a = 0, b = N;
+      while (a < b) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (er_rev[(S + mid) % ring_cap] >= e.rev) b = mid; else a = mid + 1;
+      }
+      lo = S + a;
+      const int64_t cnt = N - a, g0 = kbwreg::G0(lo, S);
+      const int64_t nown = kbwreg::OwnWords(cnt);
+      const int sh = kbwreg::Shift(lo, S);
+      const uint64_t* G = scratch + (int64_t)w * gwords;
+      for (int64_t i0 = 0; i0 < nown; i0 += 64) {
+        const int64_t i = i0 + lane;
+        uint64_t word = 0;
+        if (i < nown)
+          word = kbwreg::MaskWord(kbwreg::OwnWord(G, gwords, g0, sh, i),
+                                  (int)(i & 7), kbwreg::RefCount(cnt, i >> 3));
+        nrefs += (uint32_t)kbwreg::NonEmptyRefs(__ballot(word != 0));
+        pend += (uint64_t)__popcll(word);
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) pend += wp_shfl64(pend, lane ^ d);
+      if (pend > 0) from = newest_rev + 1;  // watch.go:91-95
+    }
+    if (lane == 0) {
+      uint64_t* d = hdr + 2 + 4 * (int64_t)w;
+      d[0] = nrefs;
+      d[1] = from;
+      d[2] = pend;
+      d[3] = 0;
+      wlo[w] = lo;
+    }
+    if (e.slot >= 0 && e.slot < wcap) {
+      if (lane < KEYW / 8)
+        ((uint64_t*)(wpfx + e.slot * KEYW))[lane] = ((const uint64_t*)e.pfx)[lane];
+      if (lane == 0) {
+        wplen[e.slot] = e.plen;
+        wfrom[e.slot] = from;
+        wlive[e.slot] = 1;
+      }
+    }
+  }
+  __shared__ bool is_last;
+  __shared__ uint64_t wsum[4], wpend[4];
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+  __syncthreads();
+  if (!is_last) return;
+  __threadfence();
+  uint64_t base = 0, pend_all = 0;  // block-uniform running totals
+  for (int c0 = 0; c0 < nw; c0 += 256) {
+    const int q = c0 + threadIdx.x;
+    uint64_t nr = 0, pe = 0;
+    if (q < nw) {
+      uint64_t* d = hdr + 2 + 4 * (int64_t)q;
+      nr = __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      pe = __hip_atomic_load(d + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const uint64_t incl = wp_scan64(nr, lane);
+    const uint64_t pincl = wp_scan64(pe, lane);
+    if (lane == 63) { wsum[wv] = incl; wpend[wv] = pincl; }
+    __syncthreads();
+    uint64_t woff = 0, tot = 0, ptot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < wv) woff += wsum[k];
+      tot += wsum[k];
+      ptot += wpend[k];
+    }
+    if (q < nw) hdr[2 + 4 * (int64_t)q + 3] = base + woff + incl - nr;
+    base += tot;
+    pend_all += ptot;
+    __syncthreads();  // wsum / wpend reused by the next pass
+  }
+  if (threadIdx.x == 0) {
+    hdr[0] = base;
+    hdr[1] = pend_all;
+    *ticket = 0;
+  }
+}
+
+// one wave per watcher with refs, four per block: the walk of k_wreg_plan
+// again, now writing. Lane l of a round holds own word i0 + l = word l & 7 of
+// ref (i0 + l) >> 3; a non-empty ref's eight lanes store its words, the first
+// of them also base = lo + 512 c and count = min(512, cnt - 512 c). Refs land
+// compactly in ascending c from the watcher's ref_off. A ref index outside
+// the watcher's planned count or the ref buffer is not written.
+__global__ __launch_bounds__(256) void k_wreg_emit(
+    const uint64_t* __restrict__ scratch, int64_t gwords, int64_t S, int64_t N,
+    const int64_t* __restrict__ wlo, const uint64_t* __restrict__ hdr, int nw,
+    WpollRef* __restrict__ refs, int64_t refs_cap) {
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= nw) return;  // wave-uniform
+  const uint64_t* d = hdr + 2 + 4 * (int64_t)w;
+  const int64_t nrefs = (int64_t)(uint32_t)d[0], off = (int64_t)d[3];
+  if (nrefs == 0) return;
+  const int64_t lo = wlo[w], cnt = S + N - lo, g0 = kbwreg::G0(lo, S);
+  const int64_t nown = kbwreg::OwnWords(cnt);
+  const int sh = kbwreg::Shift(lo, S);
+  const uint64_t* G = scratch + (int64_t)w * gwords;
+  int64_t done = 0;
+  for (int64_t i0 = 0; i0 < nown; i0 += 64) {
+    const int64_t i = i0 + lane, c = i >> 3;
+    const int k = (int)(i & 7), r = lane >> 3;
+    const int32_t count = kbwreg::RefCount(cnt, c);
+    uint64_t word = 0;
+    if (i < nown)
+      word = kbwreg::MaskWord(kbwreg::OwnWord(G, gwords, g0, sh, i), k, count);
+    const uint64_t m = __ballot(word != 0);
+    if ((m >> (8 * r)) & 0xff) {
+      const int64_t idx = done + kbwreg::NonEmptyRefsBelow(m, r);
+      if (idx < nrefs && off + idx < refs_cap) {
+        WpollRef* o = refs + off + idx;
+        o->words[k] = word;
+        if (k == 0) {
+          o->base = lo + kbwreg::kRefEvents * c;
+          o->count = count;
+          o->widx = w;
+        }
+      }
+    }
+    done += kbwreg::NonEmptyRefs(m);
+  }
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -2165,6 +2468,77 @@ struct Slab::Impl {
     HIP_CHECK(hipHostMalloc(&h_wsizes, cap * sizeof(WpollSize)));
     HIP_CHECK(hipHostMalloc(&h_woffs, cap * 8));
     wrefs_cap = cap;
+    return true;
+  }
+
+  // batched watch registration (allocated on first use, grown on demand):
+  // staged entries, the dense scratch bitmap [watcher][gword], per-watcher
+  // lo, the directory, the compact refs and the plan kernel's ticket
+  int64_t wreg_cfg_bytes = kbwreg::kDefaultBytes;  // KB_WATCH_REG_BYTES
+  WregEntry *h_went = nullptr, *d_went = nullptr;
+  int64_t* d_wreg_lo = nullptr;
+  uint64_t *d_wreg_hdr = nullptr, *h_wreg_hdr = nullptr;
+  int64_t went_cap = 0;
+  uint64_t* d_wreg_scratch = nullptr;
+  int64_t wreg_scratch_cap = 0;  // words
+  WpollRef *d_wreg_refs = nullptr, *h_wreg_refs = nullptr;
+  int64_t wreg_drefs_cap = 0, wreg_hrefs_cap = 0;
+  unsigned int* d_wreg_ticket = nullptr;
+  hipEvent_t ev_wr0 = nullptr, ev_wr1 = nullptr;
+  void free_wreg() {
+    for (void* q : {(void*)d_went, (void*)d_wreg_lo, (void*)d_wreg_hdr,
+                    (void*)d_wreg_scratch, (void*)d_wreg_refs,
+                    (void*)d_wreg_ticket})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_went, (void*)h_wreg_hdr, (void*)h_wreg_refs})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_wr0, ev_wr1})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_went(int64_t nw, std::string* err) {
+    if (!d_wreg_ticket) {
+      HIP_CHECK(hipEventCreate(&ev_wr0));
+      HIP_CHECK(hipEventCreate(&ev_wr1));
+      HIP_CHECK(hipMalloc(&d_wreg_ticket, 4));
+      HIP_CHECK(hipMemsetAsync(d_wreg_ticket, 0, 4, stream));
+    }
+    if (nw <= went_cap) return true;
+    const int64_t cap = std::max<int64_t>(1024, nw + nw / 2);
+    for (void* q : {(void*)d_went, (void*)d_wreg_lo, (void*)d_wreg_hdr})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_went, (void*)h_wreg_hdr})
+      if (q) (void)hipHostFree(q);
+    d_went = nullptr; d_wreg_lo = nullptr; d_wreg_hdr = nullptr;
+    h_went = nullptr; h_wreg_hdr = nullptr;
+    went_cap = 0;
+    HIP_CHECK(hipMalloc(&d_went, cap * sizeof(WregEntry)));
+    HIP_CHECK(hipMalloc(&d_wreg_lo, cap * 8));
+    HIP_CHECK(hipMalloc(&d_wreg_hdr, 16 + cap * sizeof(WregDir)));
+    HIP_CHECK(hipHostMalloc(&h_went, cap * sizeof(WregEntry)));
+    HIP_CHECK(hipHostMalloc(&h_wreg_hdr, 16 + cap * sizeof(WregDir)));
+    went_cap = cap;
+    return true;
+  }
+  bool grow_watchers(int64_t slot, std::string* err) {
+    if (slot < wcap) return true;
+    int64_t cap = std::max<int64_t>(1024, slot + slot / 2 + 1);
+    uint8_t* npfx; uint32_t *nplen, *nlive; uint64_t* nfrom;
+    HIP_CHECK(hipMalloc(&npfx, cap * KEYW));
+    HIP_CHECK(hipMalloc(&nplen, cap * 4));
+    HIP_CHECK(hipMalloc(&nlive, cap * 4));
+    HIP_CHECK(hipMalloc(&nfrom, cap * 8));
+    HIP_CHECK(hipMemsetAsync(nlive, 0, cap * 4, stream));
+    if (wcap > 0) {
+      HIP_CHECK(hipMemcpyAsync(npfx, d_wpfx, wcap * KEYW, hipMemcpyDeviceToDevice, stream));
+      HIP_CHECK(hipMemcpyAsync(nplen, d_wplen, wcap * 4, hipMemcpyDeviceToDevice, stream));
+      HIP_CHECK(hipMemcpyAsync(nlive, d_wlive, wcap * 4, hipMemcpyDeviceToDevice, stream));
+      HIP_CHECK(hipMemcpyAsync(nfrom, d_wfrom, wcap * 8, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (void* q : {(void*)d_wpfx, (void*)d_wplen, (void*)d_wlive, (void*)d_wfrom})
+      if (q) (void)hipFree(q);
+    d_wpfx = npfx; d_wplen = nplen; d_wlive = nlive; d_wfrom = nfrom;
+    wcap = cap;
     return true;
   }
 
@@ -2392,6 +2766,7 @@ struct Slab::Impl {
       if (p) (void)hipFree(p);
     }
     free_wpoll();
+    free_wreg();
     free_list();
     free_getb();
     free_count();
@@ -2647,6 +3022,8 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   I->scan_t &= ~63;
   I->max_cap = env_i64("KB_MAX_CAP", 4352);
   I->arena_bytes = env_i64("KB_ARENA_BYTES", 384ll << 20);
+  I->wreg_cfg_bytes = env_i64("KB_WATCH_REG_BYTES", kbwreg::kDefaultBytes);
+  if (I->wreg_cfg_bytes < 8) I->wreg_cfg_bytes = 8;
   I->count_tile = kbcount::ClampTile(env_i64("KB_COUNT_TILE", kbcount::kDefaultTile));
   {
     int cus = 0;
@@ -3956,26 +4333,7 @@ bool Slab::Dump(std::vector<DumpRow>* rows_out, std::string* err) {
 bool Slab::WatcherSet(int64_t slot, const uint8_t* prefix, uint32_t plen,
                       uint64_t from_rev, std::string* err) {
   Impl* I = p;
-  if (slot >= I->wcap) {
-    int64_t cap = std::max<int64_t>(1024, slot + slot / 2 + 1);
-    uint8_t* npfx; uint32_t *nplen, *nlive; uint64_t* nfrom;
-    HIP_CHECK(hipMalloc(&npfx, cap * KEYW));
-    HIP_CHECK(hipMalloc(&nplen, cap * 4));
-    HIP_CHECK(hipMalloc(&nlive, cap * 4));
-    HIP_CHECK(hipMalloc(&nfrom, cap * 8));
-    HIP_CHECK(hipMemsetAsync(nlive, 0, cap * 4, I->stream));
-    if (I->wcap > 0) {
-      HIP_CHECK(hipMemcpyAsync(npfx, I->d_wpfx, I->wcap * KEYW, hipMemcpyDeviceToDevice, I->stream));
-      HIP_CHECK(hipMemcpyAsync(nplen, I->d_wplen, I->wcap * 4, hipMemcpyDeviceToDevice, I->stream));
-      HIP_CHECK(hipMemcpyAsync(nlive, I->d_wlive, I->wcap * 4, hipMemcpyDeviceToDevice, I->stream));
-      HIP_CHECK(hipMemcpyAsync(nfrom, I->d_wfrom, I->wcap * 8, hipMemcpyDeviceToDevice, I->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(I->stream));
-    for (void* q : {(void*)I->d_wpfx, (void*)I->d_wplen, (void*)I->d_wlive, (void*)I->d_wfrom})
-      if (q) (void)hipFree(q);
-    I->d_wpfx = npfx; I->d_wplen = nplen; I->d_wlive = nlive; I->d_wfrom = nfrom;
-    I->wcap = cap;
-  }
+  if (!I->grow_watchers(slot, err)) return false;
   uint8_t buf[KEYW] = {0};
   memcpy(buf, prefix, plen > KEYW ? KEYW : plen);
   uint32_t one = 1;
@@ -4119,6 +4477,117 @@ bool Slab::WatchCatchup(const uint8_t* pfx96, uint32_t plen, uint64_t from_rev,
   perf.filter_launches++;
   perf.filter_events += count;
   perf.filter_watchers += 1;
+  return true;
+}
+
+// ---- batched watch registration (kb_watch_batch) ---------------------------
+
+int64_t Slab::wreg_bytes() const { return p->wreg_cfg_bytes; }
+
+bool Slab::WatcherReserve(int64_t slot, std::string* err) {
+  return p->grow_watchers(slot, err);
+}
+
+WregEntry* Slab::WregStaging(int64_t nw, std::string* err) {
+  if (!p->ensure_went(nw, err)) return nullptr;
+  return p->h_went;
+}
+
+bool Slab::WatchRegLaunch(int nw, int nscan, int64_t S, int64_t N,
+                          uint64_t newest_rev, const WregHdr** hdr,
+                          const WpollRef** refs, std::string* err) {
+  Impl* I = p;
+  *hdr = nullptr;
+  *refs = nullptr;
+  if (nw <= 0 || nw > I->went_cap || nscan < 0 || nscan > nw || N < 0 ||
+      N > I->er_cap || S < 0 || (nscan > 0 && (N == 0 || !I->er_keys))) {
+    if (err) *err = "watch batch: bad sub-batch";
+    return false;
+  }
+  // every staged slot must lie inside the table: WatcherReserve came first
+  for (int i = 0; i < nw; ++i)
+    if (I->h_went[i].slot < 0 || I->h_went[i].slot >= I->wcap) {
+      if (err) *err = "watch batch: slot outside the watcher table";
+      return false;
+    }
+  const int64_t gwords = nscan > 0 ? kbwreg::GWords(N) : 0;
+  const int64_t runs = ceil_div(gwords, WREG_RUN);
+  if (runs > 65535) {
+    if (err) *err = "watch batch: ring span too large for the scan grid";
+    return false;
+  }
+  const int64_t need_words = std::max<int64_t>(1, (int64_t)nw * gwords);
+  if (need_words > I->wreg_scratch_cap) {
+    if (I->d_wreg_scratch) (void)hipFree(I->d_wreg_scratch);
+    I->d_wreg_scratch = nullptr;
+    I->wreg_scratch_cap = 0;
+    HIP_CHECK(hipMalloc(&I->d_wreg_scratch, need_words * 8));
+    I->wreg_scratch_cap = need_words;
+  }
+  // a watcher has at most ceil(N / 512) <= gwords / 8 + 1 refs
+  const int64_t need_refs = std::max<int64_t>(1, (int64_t)nw * (gwords / 8 + 1));
+  if (need_refs > I->wreg_drefs_cap) {
+    if (I->d_wreg_refs) (void)hipFree(I->d_wreg_refs);
+    I->d_wreg_refs = nullptr;
+    I->wreg_drefs_cap = 0;
+    HIP_CHECK(hipMalloc(&I->d_wreg_refs, need_refs * sizeof(WpollRef)));
+    I->wreg_drefs_cap = need_refs;
+  }
+  HIP_CHECK(hipMemcpyAsync(I->d_went, I->h_went, (int64_t)nw * sizeof(WregEntry),
+                           hipMemcpyHostToDevice, I->stream));
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  HIP_CHECK(hipEventRecord(I->ev_wr0, I->stream));
+  hipLaunchKernelGGL(k_wreg_scan,
+                     dim3((uint32_t)ceil_div(nw, 64),
+                          (uint32_t)std::max<int64_t>(1, runs)),
+                     dim3(256), 0, I->stream, I->er_keys, I->er_rev, I->er_cap,
+                     S, N, I->d_went, nw, I->d_wreg_scratch, gwords);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_wreg_plan, dim3((uint32_t)ceil_div(nw, 4)), dim3(256), 0,
+                     I->stream, I->er_rev, I->er_cap, S, N, newest_rev,
+                     I->d_went, nw, I->d_wreg_scratch, gwords, I->d_wpfx,
+                     I->d_wplen, I->d_wfrom, I->d_wlive, I->wcap, I->d_wreg_lo,
+                     I->d_wreg_hdr, I->d_wreg_ticket);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_wreg_emit, dim3((uint32_t)ceil_div(nw, 4)), dim3(256), 0,
+                     I->stream, I->d_wreg_scratch, gwords, S, N, I->d_wreg_lo,
+                     I->d_wreg_hdr, nw, I->d_wreg_refs, I->wreg_drefs_cap);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_wr1, I->stream));
+  // the directory: two totals and 32 B per watcher
+  HIP_CHECK(hipMemcpyAsync(I->h_wreg_hdr, I->d_wreg_hdr,
+                           16 + (int64_t)nw * sizeof(WregDir),
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_wr0, I->ev_wr1);
+  perf.wreg_ms += ms;
+  perf.wreg_launches += 3;
+  if (nscan > 0) perf.wreg_events_scanned += N;
+  const WregHdr* h = (const WregHdr*)I->h_wreg_hdr;
+  const int64_t total = (int64_t)h->total_refs;
+  if (total < 0 || total > I->wreg_drefs_cap) {
+    if (err) *err = "watch batch: ref total outside the ref buffer";
+    return false;
+  }
+  if (total > 0) {
+    if (total > I->wreg_hrefs_cap) {
+      if (I->h_wreg_refs) (void)hipHostFree(I->h_wreg_refs);
+      I->h_wreg_refs = nullptr;
+      I->wreg_hrefs_cap = 0;
+      const int64_t cap = std::max<int64_t>(4096, total + total / 2);
+      HIP_CHECK(hipHostMalloc(&I->h_wreg_refs, cap * sizeof(WpollRef)));
+      I->wreg_hrefs_cap = cap;
+    }
+    // the compact ref span
+    HIP_CHECK(hipMemcpyAsync(I->h_wreg_refs, I->d_wreg_refs,
+                             total * sizeof(WpollRef), hipMemcpyDeviceToHost,
+                             I->stream));
+    HIP_CHECK(hipStreamSynchronize(I->stream));
+  }
+  perf.wreg_refs += total;
+  *hdr = h;
+  *refs = I->h_wreg_refs;
   return true;
 }
 

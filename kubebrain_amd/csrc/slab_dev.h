@@ -123,6 +123,13 @@ struct Perf {
   double wpoll_ms = 0, wpoll_d2h_ms = 0;
   int64_t wpoll_launches = 0, wpoll_events_dev = 0, wpoll_events_host = 0,
           wpoll_bytes = 0;
+  // batched watch registration (kb_watch_batch): k_wreg_scan + k_wreg_plan +
+  // k_wreg_emit kernel time and launches, watchers per path (device catch-up,
+  // host bits for a prefix > 96 B, no catch-up), ring events the scans
+  // covered (the span, once per sub-batch that scanned) and refs built
+  double wreg_ms = 0;
+  int64_t wreg_launches = 0, wreg_watchers_dev = 0, wreg_watchers_host = 0,
+          wreg_watchers_nocatchup = 0, wreg_events_scanned = 0, wreg_refs = 0;
   // batched List (kb_list_batch): k_list_size + k_list_emit kernel time, the
   // section D2H, queries per path, kvs and device bytes moved
   double list_ms = 0, list_d2h_ms = 0;
@@ -196,7 +203,28 @@ struct CountBatchHdr {
   uint64_t tiles, rows, tiles_planned, rows_planned;
   uint64_t count[1];  // nq entries
 };
-
+// batched watch registration (kb_watch_batch): one entry of a
+// sub-batch as the host stages it, and what k_wreg_plan leaves per watcher
+struct WregEntry {
+  uint8_t pfx[KEYW];  // zero-padded prefix, first KEYW bytes
+  uint32_t plen;      // capped at KEYW
+  uint32_t flags;     // WREG_SCAN
+  uint64_t rev;       // WREG_SCAN: the requested revision; else the final from_rev
+  int64_t slot;       // watcher table slot the entry takes
+  uint64_t _pad;
+};
+constexpr uint32_t WREG_SCAN = 1;  // catch-up bits come from k_wreg_scan
+struct WregDir {
+  uint32_t nrefs, _pad;
+  uint64_t from_rev, pend_events, ref_off;
+};
+struct WregHdr {
+  uint64_t total_refs, total_pending;
+  WregDir dir[1];  // nw entries
+};
+static_assert(sizeof(WregEntry) == 128, "staged watcher entry layout");
+static_assert(sizeof(WregDir) == 32 && sizeof(WregHdr) == 48,
+              "watch registration directory layout");
 
 
 class Slab {
@@ -421,6 +449,22 @@ class Slab {
 
   bool WatcherSet(int64_t slot, const uint8_t* prefix, uint32_t plen,
                   uint64_t from_rev, std::string* err);  // slot grows table
+  // batched registration (kb_watch_batch). WatcherReserve
+  // grows the watcher table once to hold `slot`. WregStaging returns pinned
+  // memory for nw entries (contents are not preserved on growth).
+  // WatchRegLaunch uploads the staged sub-batch with one H2D and runs
+  // k_wreg_scan, k_wreg_plan and k_wreg_emit back to back over the resident
+  // ring span [S, S + N): the catch-up bits of the nscan WREG_SCAN entries,
+  // every entry's table row (prefix96, plen, from_rev, live = 1) and the
+  // compact ref span. One D2H brings the directory, one more the refs; *hdr
+  // and *refs point into pinned memory valid until the next call. scratch
+  // bytes bound the dense bitmap: nw * ceil(N / 64) * 8 must fit.
+  bool WatcherReserve(int64_t slot, std::string* err);
+  WregEntry* WregStaging(int64_t nw, std::string* err);
+  bool WatchRegLaunch(int nw, int nscan, int64_t S, int64_t N,
+                      uint64_t newest_rev, const WregHdr** hdr,
+                      const WpollRef** refs, std::string* err);
+  int64_t wreg_bytes() const;  // KB_WATCH_REG_BYTES
   void WatcherClear(int64_t slot);
 
   Perf perf;

@@ -965,6 +965,206 @@ Status Store::WatchPollBatch(const int64_t* wids, size_t n, uint8_t* out,
   return OK;
 }
 
+// ---- batched registration (kb_watch_batch) ----------------
+
+Status Store::WatchBatch(const uint8_t* wbuf, size_t wbuf_len, size_t n,
+                         int flags, int64_t* wids, int32_t* statuses,
+                         uint64_t* total_pending, std::string* errp) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  if (total_pending) *total_pending = 0;
+  if (flags != 0 || n > 0x7fffffffull) return INVALID_ARG;
+  struct Ent {
+    const uint8_t* pfx;
+    uint32_t plen;
+    uint64_t rev;
+    int64_t slot = -1;
+    bool scan = false, hostbits = false;
+    Watcher w;
+  };
+  std::vector<Ent> ents(n);
+  {
+    size_t off = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (wbuf_len - off < 12) return INVALID_ARG;
+      memcpy(&ents[i].plen, wbuf + off, 4);
+      memcpy(&ents[i].rev, wbuf + off + 4, 8);
+      off += 12;
+      if (wbuf_len - off < ents[i].plen) return INVALID_ARG;
+      ents[i].pfx = wbuf + off;
+      off += ents[i].plen;
+    }
+  }
+  pumpEvents();  // older events go only to older watchers
+  std::string errl;
+  std::string& err = errp ? *errp : errl;
+  kbslab::Perf& perf = slab_->perf;
+
+  // pass 1: Watch's own decisions per entry (watch.go:37-99, ring.go:84-118),
+  // slots in the order Watch would have handed them out
+  const int64_t S = ring_.s, N = ring_.e - ring_.s;
+  const uint64_t newest = N ? ring_.arr[(ring_.e - 1) % ring_.l].revision : 0;
+  const uint64_t oldest = N ? ring_.arr[ring_.s % ring_.l].revision : 0;
+  std::vector<size_t> ok;  // entries that register
+  int64_t max_slot = -1;
+  for (size_t i = 0; i < n; ++i) {
+    Ent& e = ents[i];
+    e.w.prefix.assign((const char*)e.pfx, e.plen);
+    e.w.from_rev = e.rev;
+    statuses[i] = OK;
+    wids[i] = -1;
+    if (e.rev != 0) {
+      if (N == 0) {
+        if (e.rev <= committed_) { statuses[i] = WATCH_EMPTY; continue; }
+      } else if (e.rev > newest) {
+        // high: from_rev = the requested revision
+      } else if (e.rev < oldest) {
+        statuses[i] = WATCH_LOW;  // watch.go:79-84
+        continue;
+      } else if (e.plen <= (uint32_t)KEYW) {
+        e.scan = true;
+      } else {
+        // a prefix longer than the 96B filter column: exact bits on the host,
+        // as Watch computes them
+        e.hostbits = true;
+        int64_t lo = 0, hi = N;
+        while (lo < hi) {
+          int64_t mid = lo + (hi - lo) / 2;
+          if (ring_.arr[(S + mid) % ring_.l].revision >= e.rev) hi = mid;
+          else lo = mid + 1;
+        }
+        const int64_t base = S + lo, cnt = N - lo;
+        for (int64_t c0 = 0; c0 < cnt; c0 += 512) {
+          PendRef pr{};
+          pr.base = base + c0;
+          pr.count = (int32_t)std::min<int64_t>(512, cnt - c0);
+          int64_t got = 0;
+          for (int64_t j = 0; j < pr.count; ++j) {
+            const Event& ev = ring_.arr[(pr.base + j) % ring_.l];
+            if (ev.kv_key.compare(0, e.w.prefix.size(), e.w.prefix) == 0) {
+              pr.words[j >> 6] |= 1ull << (j & 63);
+              ++got;
+            }
+          }
+          if (got) {
+            e.w.prefs.push_back(pr);
+            e.w.pend_events += got;
+          }
+        }
+        if (e.w.pend_events > 0) e.w.from_rev = newest + 1;  // watch.go:91-95
+      }
+    }
+    if (!free_slots_.empty()) { e.slot = free_slots_.back(); free_slots_.pop_back(); }
+    else e.slot = next_slot_++;
+    e.w.slot = e.slot;
+    max_slot = std::max(max_slot, e.slot);
+    ok.push_back(i);
+  }
+
+  // pass 2: sub-batches through the three kernels. A device failure gives
+  // every entry from that sub-batch on KB_EINTERNAL and returns its slot.
+  const int64_t gwords = kbwreg::GWords(N);
+  const size_t per = (size_t)kbwreg::SubBatch(slab_->wreg_bytes(), gwords);
+  size_t failed_from = ok.size();
+  if (!ok.empty() && !slab_->WatcherReserve(max_slot, &err)) failed_from = 0;
+  for (size_t b0 = 0; b0 < failed_from; b0 += per) {
+    const size_t cnt = std::min(per, ok.size() - b0);
+    kbslab::WregEntry* st = slab_->WregStaging((int64_t)cnt, &err);
+    if (!st) { failed_from = b0; break; }
+    int nscan = 0;
+    for (size_t k = 0; k < cnt; ++k) {
+      const Ent& e = ents[ok[b0 + k]];
+      kbslab::WregEntry& t = st[k];
+      memset(&t, 0, sizeof(t));
+      t.plen = std::min<uint32_t>(e.plen, (uint32_t)KEYW);
+      memcpy(t.pfx, e.pfx, t.plen);
+      t.flags = e.scan ? kbslab::WREG_SCAN : 0;
+      t.rev = e.scan ? e.rev : e.w.from_rev;
+      t.slot = e.slot;
+      nscan += e.scan ? 1 : 0;
+    }
+    const kbslab::WregHdr* hdr = nullptr;
+    const kbslab::WpollRef* refs = nullptr;
+    if (!slab_->WatchRegLaunch((int)cnt, nscan, S, N, newest, &hdr, &refs, &err)) {
+      failed_from = b0;
+      break;
+    }
+    // the directory must describe the ref span it came with
+    uint64_t at = 0;
+    bool sane = true;
+    for (size_t k = 0; k < cnt && sane; ++k) {
+      const kbslab::WregDir& d = hdr->dir[k];
+      const Ent& e = ents[ok[b0 + k]];
+      sane = d.ref_off == at && (e.scan || d.nrefs == 0) &&
+             (e.scan || d.from_rev == e.w.from_rev);
+      for (uint32_t r = 0; r < d.nrefs && sane; ++r)
+        sane = refs[at + r].widx == (int32_t)k;
+      at += d.nrefs;
+    }
+    if (!sane || at != hdr->total_refs) {
+      err = "watch batch: device directory and ref span disagree";
+      failed_from = b0;
+      break;
+    }
+    for (size_t k = 0; k < cnt; ++k) {
+      Ent& e = ents[ok[b0 + k]];
+      if (!e.scan) continue;
+      const kbslab::WregDir& d = hdr->dir[k];
+      e.w.from_rev = d.from_rev;
+      e.w.pend_events = (int64_t)d.pend_events;
+      for (uint32_t r = 0; r < d.nrefs; ++r) {
+        const kbslab::WpollRef& s = refs[d.ref_off + r];
+        PendRef pr;
+        pr.base = s.base;
+        pr.count = s.count;
+        memcpy(pr.words, s.words, sizeof(pr.words));
+        e.w.prefs.push_back(pr);
+      }
+    }
+  }
+
+  // pass 3: ids in entry order, as consecutive Watch calls would give them
+  uint64_t total = 0;
+  for (size_t k = 0; k < failed_from; ++k) {
+    Ent& e = ents[ok[k]];
+    if (e.scan) perf.wreg_watchers_dev++;
+    else if (e.hostbits) perf.wreg_watchers_host++;
+    else perf.wreg_watchers_nocatchup++;
+    total += (uint64_t)e.w.pend_events;
+    const int64_t wid = next_wid_++;
+    wids[ok[k]] = wid;
+    watchers_[wid] = std::move(e.w);
+  }
+  // the reserved slots of failed entries must not leak
+  for (size_t k = ok.size(); k > failed_from; --k) {
+    Ent& e = ents[ok[k - 1]];
+    statuses[ok[k - 1]] = INTERNAL;
+    slab_->WatcherClear(e.slot);
+    free_slots_.push_back(e.slot);
+  }
+  if (total_pending) *total_pending = total;
+  return OK;
+}
+
+Status Store::TestWatchRefs(int64_t wid, std::string* wire) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  auto it = watchers_.find(wid);
+  if (it == watchers_.end()) return WATCH_DROPPED;
+  const Watcher& w = it->second;
+  auto put = [&](const void* p, size_t n) { wire->append((const char*)p, n); };
+  const uint32_t nrefs = (uint32_t)w.prefs.size();
+  put(&nrefs, 4);
+  put(&w.from_rev, 8);
+  put(&w.pend_events, 8);
+  for (const PendRef& pr : w.prefs) {
+    const int32_t zero = 0;
+    put(&pr.base, 8);
+    put(&pr.count, 4);
+    put(&zero, 4);
+    put(pr.words, sizeof(pr.words));
+  }
+  return OK;
+}
+
 void Store::WatchCancel(int64_t wid) {
   std::lock_guard<std::recursive_mutex> lk(mu_);
   auto it = watchers_.find(wid);
@@ -2436,6 +2636,16 @@ std::string Store::PerfJson() {
            (long long)p.list_batch_q_host, (long long)p.list_batch_kvs,
            (long long)p.list_batch_bytes, (long long)p.list_emit_launches,
            p.list_ms, p.list_d2h_ms, (long long)p.gather_launches);
+  // kb_watch_batch: 142 fixed characters, 6 integers and 1 float more, i.e.
+  // 2406 + 142 + 7 * 20 = 2688 characters at worst: still under the buffer
+  at += snprintf(buf + at, sizeof(buf) - (size_t)at,
+           "\"wreg_launches\":%lld,\"wreg_watchers_dev\":%lld,"
+           "\"wreg_watchers_host\":%lld,\"wreg_watchers_nocatchup\":%lld,"
+           "\"wreg_events_scanned\":%lld,\"wreg_refs\":%lld,\"wreg_ms\":%.3f,",
+           (long long)p.wreg_launches, (long long)p.wreg_watchers_dev,
+           (long long)p.wreg_watchers_host,
+           (long long)p.wreg_watchers_nocatchup,
+           (long long)p.wreg_events_scanned, (long long)p.wreg_refs, p.wreg_ms);
   snprintf(buf + at, sizeof(buf) - (size_t)at,
            "\"wpoll_ms\":%.3f,\"wpoll_d2h_ms\":%.3f,\"wpoll_launches\":%lld,"
            "\"wpoll_events_dev\":%lld,\"wpoll_events_host\":%lld,"

@@ -23,6 +23,7 @@
 #include "lplan.h"
 #include "slab_dev.h"
 #include "wpoll.h"
+#include "wreg.h"
 
 namespace kbstore {
 
@@ -130,6 +131,19 @@ class Store {
   Status WatchPollBatch(const int64_t* wids, size_t n, uint8_t* out, size_t cap,
                         size_t* out_len, uint64_t* total_events,
                         std::string* err = nullptr);
+  // batched registration (kb_watch_batch): n Watch calls under one mutex
+  // hold and one pumpEvents; catch-up bits, refs and the watcher table rows
+  // come from the device. wbuf = n x {u32 plen; u64 rev;
+  // prefix} in wbuf_len bytes; wids[i] / statuses[i] are what Watch(prefix_i,
+  // rev_i) would have returned in that order. A blob that runs out of bytes
+  // is INVALID_ARG and registers nothing.
+  Status WatchBatch(const uint8_t* wbuf, size_t wbuf_len, size_t n, int flags,
+                    int64_t* wids, int32_t* statuses, uint64_t* total_pending,
+                    std::string* err = nullptr);
+  // test hook (kb_test_watch_refs): a watcher's pending refs as u32 nrefs;
+  // u64 from_rev; i64 pend_events; nrefs x {i64 base; i32 count; i32 0; u64
+  // words[8]}. Launches nothing, changes nothing.
+  Status TestWatchRefs(int64_t wid, std::string* wire);
   void WatchCancel(int64_t wid);
 
   void ClockAdvance(int64_t secs);
