@@ -299,6 +299,44 @@ long long kb_stream_open(kb_store*, const uint8_t* start, size_t slen,
 /* out = packed kvs like kb_list; an EMPTY batch is the end marker */
 int kb_stream_next(kb_store*, long long sid, uint8_t* out, size_t cap,
                    size_t* out_len);
+/* The next kvs of stream sid, many per call (ListByStream, range.go:247-256;
+ * the 300-kv channel batches of receiver.go:118-150 are cut from one reply by
+ * the binding). Advances the same stream state as kb_stream_next, so the two
+ * calls may alternate freely on one sid.
+ * out = the kb_list wire: u32 n; n x {u64 rev; u32 klen; key; u32 vlen; val},
+ * the next n kvs of the stream at its pinned read_rev in key order.
+ * Concatenated over all calls the records are byte for byte those a
+ * kb_stream_next loop returns, whatever mixture of the two calls is used.
+ * n <= max_kvs; max_kvs <= 0 or above the library's maximum means that
+ * maximum (env KB_STREAM_MAX_KVS, default 65536); 4 + record bytes <= cap.
+ * A reply MAY BE SHORTER than these bounds allow: the call scans the range in
+ * windows of KB_STREAM_WINDOW base rows (a multiple of 64, at least 64,
+ * clamped like KB_COUNT_TILE; default 256K) and stops at the first window
+ * boundary at which max_kvs or the byte budget is reached, and the records
+ * of one reply never exceed the gather arena (KB_ARENA_BYTES). A reply is
+ * empty (u32 0) only as the end marker.
+ * *more = 1 while the range may hold more, 0 on the reply that reached the
+ * end of the range: after it the stream is in the state kb_stream_next
+ * leaves after its last non-empty batch, i.e. the next call of either kind
+ * returns the empty end marker and frees the stream. An empty first reply
+ * frees the stream at once. *n_kvs = n.
+ * flags bit 0 = keys_only: every record carries vlen = 0 and no value bytes,
+ * as in kb_list_batch. Any other bit: KB_EINVALID.
+ * KB_ENOBUF (cap cannot hold even the next record, or cap < 4): *out_len =
+ * 4 + that record's size (4 for the end marker), nothing is written and the
+ * stream is unchanged: the same call with a larger buffer returns that record
+ * first. Unknown sid: KB_EINVALID. Compaction past read_rev: KB_ECOMPACTED
+ * and the stream is freed, as kb_stream_next does on every call.
+ * The winners of both runs are found, merged in key order and serialized by
+ * HIP kernels across the whole chip; a single record larger
+ * than the arena is served for that one record by kb_stream_next's own path
+ * with identical bytes. One mutex hold; a pending pipelined kb_bench_step
+ * batch is collected first. The call reuses the gather arena, so
+ * kb_test_last_range reports an EMPTY batch (u32 0) afterwards, as after
+ * kb_list_batch. */
+int kb_stream_next_batch(kb_store*, long long sid, long long max_kvs, int flags,
+                         uint8_t* out, size_t cap, size_t* out_len,
+                         unsigned long long* n_kvs, int* more);
 void kb_stream_close(kb_store*, long long sid);
 int kb_partitions(kb_store*, const uint8_t* start, size_t slen,
                   const uint8_t* end, size_t elen, uint8_t* out, size_t cap,

@@ -509,13 +509,19 @@ func (b *amdBackend) ListByStream(ctx context.Context, startKey, endKey []byte, 
 	go func() {
 		defer close(ch)
 		defer C.kb_stream_close(b.h, sid)
-		buf := make([]byte, 16<<20)
+		// one kb_stream_next_batch reply (up to KB_STREAM_MAX_KVS kvs, found
+		// and serialized on the GPU) fills many 300-kv channel batches
+		// (rangeStreamBatch, scanner.go:45). Uncompiled here like the rest
+		// of this file.
+		buf := make([]byte, 64<<20)
 		for {
 			var outLen C.size_t
-			rc := C.kb_stream_next(b.h, sid, bptr(buf), C.size_t(len(buf)),
-				&outLen)
-			if rc == C.KB_ENOBUF {
-				buf = make([]byte, int(outLen))
+			var nKvs C.ulonglong
+			var more C.int
+			rc := C.kb_stream_next_batch(b.h, sid, 0, 0, bptr(buf),
+				C.size_t(len(buf)), &outLen, &nKvs, &more)
+			if rc == C.KB_ENOBUF { // the next record alone needs outLen bytes
+				buf = make([]byte, 2*int(outLen))
 				continue
 			}
 			if rc != C.KB_OK {
@@ -523,15 +529,22 @@ func (b *amdBackend) ListByStream(ctx context.Context, startKey, endKey []byte, 
 				return
 			}
 			kvs := decodeKvs(buf[:outLen])
-			if len(kvs) == 0 { // empty batch = end marker
+			if len(kvs) == 0 { // empty reply = end marker
 				return
 			}
-			select {
-			case ch <- &proto.StreamRangeResponse{
-				RangeResponse: &proto.RangeResponse{
-					Header: header(uint64(readRev)), Kvs: kvs}}:
-			case <-ctx.Done():
-				return
+			for len(kvs) > 0 {
+				n := 300
+				if n > len(kvs) {
+					n = len(kvs)
+				}
+				select {
+				case ch <- &proto.StreamRangeResponse{
+					RangeResponse: &proto.RangeResponse{
+						Header: header(uint64(readRev)), Kvs: kvs[:n]}}:
+				case <-ctx.Done():
+					return
+				}
+				kvs = kvs[n:]
 			}
 		}
 	}()

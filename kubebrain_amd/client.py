@@ -416,6 +416,42 @@ class Store:
                     return OK, batches
                 batches.append(kvs)
 
+    def stream_open(self, start: bytes, end: bytes, rev: int = 0):
+        """kb_stream_open (product ABI only) -> (status, sid, read_rev)."""
+        st = C.c_int(); rrev = C.c_uint64()
+        f = self._f("stream_open")
+        f.restype = C.c_longlong
+        sid = f(C.c_void_p(self.h), start, C.c_size_t(len(start)), end,
+                C.c_size_t(len(end)), C.c_uint64(rev), C.byref(rrev), C.byref(st))
+        return st.value, sid, rrev.value
+
+    def stream_next(self, sid: int):
+        """One kb_stream_next batch -> (rc, raw reply bytes)."""
+        out_len = C.c_size_t()
+        rc = self._f("stream_next")(C.c_void_p(self.h), C.c_longlong(sid), self.buf,
+                                    C.c_size_t(self.BUF), C.byref(out_len))
+        return rc, C.string_at(self.buf, out_len.value) if rc == OK else b""
+
+    def stream_next_batch(self, sid: int, max_kvs: int = 0, flags: int = 0,
+                          cap: int | None = None):
+        """The next kvs of a stream, many per call (kb_stream_next_batch;
+        product ABI only). flags bit 0 = keys_only. Returns (rc, raw, more,
+        n_kvs, out_len): raw is the reply in the kb_list wire (_parse_kvs reads
+        it; b"" unless rc is OK). cap = None uses the client's buffer; a given
+        cap is passed as it is, so KB_ENOBUF comes back with out_len = the size
+        the next record needs and the stream unchanged."""
+        out_len = C.c_size_t(); n = C.c_ulonglong(); more = C.c_int()
+        buf = self.buf if cap is None else C.create_string_buffer(max(cap, 1))
+        rc = self._f("stream_next_batch")(
+            C.c_void_p(self.h), C.c_longlong(sid), C.c_longlong(max_kvs),
+            C.c_int(flags), buf, C.c_size_t(self.BUF if cap is None else cap),
+            C.byref(out_len), C.byref(n), C.byref(more))
+        raw = C.string_at(buf, out_len.value) if rc == OK else b""
+        return rc, raw, more.value, n.value, out_len.value
+
+    def stream_close(self, sid: int):
+        self._f("stream_close")(C.c_void_p(self.h), C.c_longlong(sid))
+
     def partitions(self, start: bytes, end: bytes):
         out_len = C.c_size_t(); hr = C.c_uint64()
         rc = self._f("partitions")(C.c_void_p(self.h), start,

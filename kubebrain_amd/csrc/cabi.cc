@@ -426,6 +426,23 @@ int kb_stream_next(kb_store* h, long long sid, uint8_t* out, size_t cap,
   return st;
 }
 
+int kb_stream_next_batch(kb_store* h, long long sid, long long max_kvs,
+                         int flags, uint8_t* out, size_t cap, size_t* out_len,
+                         unsigned long long* n_kvs, int* more) {
+  std::string err;
+  size_t len = 0;
+  uint64_t n = 0;
+  int m = 0;
+  Status st = ((Store*)h)->StreamNextBatch(sid, max_kvs, flags, out, cap, &len,
+                                           &n, &m, &err);
+  if (out_len) *out_len = len;
+  if (n_kvs) *n_kvs = n;
+  if (more) *more = m;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
 void kb_stream_close(kb_store* h, long long sid) { ((Store*)h)->StreamClose(sid); }
 
 int kb_partitions(kb_store* h, const uint8_t* start, size_t slen,

@@ -14,6 +14,7 @@
 #include "cplan.h"
 #include "dmerge.h"
 #include "slab_dev.h"
+#include "splan.h"
 #include "stepstage.h"
 #include "wreg.h"
 
@@ -1633,15 +1634,47 @@ __global__ __launch_bounds__(256) void k_list_size(
   }
 }
 
+// the record writer of k_list_emit and k_stream_emit: one wave writes row
+// `row` of run r as {u64 rev; u32 klen; key; u32 vlen; val} at arena + dd
+// (vlen = 0 for keys_only). The destination is arbitrarily aligned; the three
+// sources (96 B key column row, key-spill tail, value heap) are 16 B aligned
+// and padded to 16, which is what wp_copy_record needs. Store-hazard rule of
+// §3.5: nothing wider than a byte leaves [dst, dst+reclen); the 12+4 header
+// bytes go out as byte stores. A record that would leave the arena, or whose
+// source lies outside the spill / value heap, is skipped, never written.
+__device__ __forceinline__ void list_write_record(
+    const Run& r, int64_t row, uint64_t m, uint32_t vlen, uint64_t dd,
+    const uint8_t* __restrict__ spill, int64_t spill_used,
+    const uint8_t* __restrict__ heap, int64_t heap_used,
+    uint8_t* __restrict__ arena, int64_t arena_cap, int lane) {
+  const uint32_t klen = meta_klen(m);
+  const uint64_t reclen = 16 + (uint64_t)klen + vlen;
+  if (dd > (uint64_t)arena_cap || reclen > (uint64_t)arena_cap - dd) return;
+  uint8_t* dst = arena + dd;
+  const uint64_t rev = r.rev[row];
+  if (lane < 8) dst[lane] = (uint8_t)(rev >> (8 * lane));
+  else if (lane < 12) dst[lane] = (uint8_t)(klen >> (8 * (lane - 8)));
+  else if (lane < 16) dst[klen + lane] = (uint8_t)(vlen >> (8 * (lane - 12)));
+  const uint32_t kin = klen > (uint32_t)KEYW ? (uint32_t)KEYW : klen;
+  wp_copy_record(r.keys + row * KEYW, dst + 12, kin, lane);
+  if (klen > (uint32_t)KEYW) {  // spill tail (keys > 96B)
+    const uint64_t ko = r.ko[row];
+    const uint32_t tl = klen - (uint32_t)KEYW;
+    if ((ko & 15) == 0 && ko + ((tl + 15) & ~15u) <= (uint64_t)spill_used)
+      wp_copy_record(spill + ko, dst + 12 + KEYW, tl, lane);
+  }
+  if (vlen) {
+    const uint64_t vo = r.vo[row];
+    if ((vo & 15) == 0 &&
+        vo + (((uint64_t)vlen + 15) & ~15ull) <= (uint64_t)heap_used)
+      wp_copy_record(heap + vo, dst + 16 + klen, vlen, lane);
+  }
+}
+
 // one wave per winner record, flat over the round's records: wave g finds
 // its query by a binary search over cum[] (records before each query), so
-// skewed batches leave no idle blocks. The destination sec_base[q] + offs is
-// arbitrarily aligned (the wire is packed); the three sources (96 B key
-// column row, key-spill tail, value heap) are 16 B aligned and padded to 16,
-// which is what wp_copy_record needs. Store-hazard rule of §3.5: nothing
-// wider than a byte leaves [dst, dst+reclen); the 12+4 header bytes go out
-// as byte stores. A record that would leave the arena, or whose source lies
-// outside the run / heap, is skipped, never written.
+// skewed batches leave no idle blocks. The record goes to sec_base[q] + offs
+// through list_write_record; a row outside its run is skipped.
 __global__ __launch_bounds__(256) void k_list_emit(
     Run rb, Run rd, int64_t n, int64_t dn,
     const uint8_t* __restrict__ spill, int64_t spill_used,
@@ -1668,30 +1701,10 @@ __global__ __launch_bounds__(256) void k_list_emit(
   if (row >= (isd ? dn : n)) return;
   const Run& r = isd ? rd : rb;
   const uint64_t m = r.meta[row];
-  const uint32_t klen = meta_klen(m);
   const uint32_t vlen = qs[q].keys_only ? 0 : meta_vlen(m);
   const uint64_t dd = sec_base[q] + offs[(int64_t)q * max_cap + (int64_t)j];
-  const uint64_t reclen = 16 + (uint64_t)klen + vlen;
-  if (dd > (uint64_t)arena_cap || reclen > (uint64_t)arena_cap - dd) return;
-  uint8_t* dst = arena + dd;
-  const uint64_t rev = r.rev[row];
-  if (lane < 8) dst[lane] = (uint8_t)(rev >> (8 * lane));
-  else if (lane < 12) dst[lane] = (uint8_t)(klen >> (8 * (lane - 8)));
-  else if (lane < 16) dst[klen + lane] = (uint8_t)(vlen >> (8 * (lane - 12)));
-  const uint32_t kin = klen > (uint32_t)KEYW ? (uint32_t)KEYW : klen;
-  wp_copy_record(r.keys + row * KEYW, dst + 12, kin, lane);
-  if (klen > (uint32_t)KEYW) {  // spill tail (keys > 96B)
-    const uint64_t ko = r.ko[row];
-    const uint32_t tl = klen - (uint32_t)KEYW;
-    if ((ko & 15) == 0 && ko + ((tl + 15) & ~15u) <= (uint64_t)spill_used)
-      wp_copy_record(spill + ko, dst + 12 + KEYW, tl, lane);
-  }
-  if (vlen) {
-    const uint64_t vo = r.vo[row];
-    if ((vo & 15) == 0 &&
-        vo + (((uint64_t)vlen + 15) & ~15ull) <= (uint64_t)heap_used)
-      wp_copy_record(heap + vo, dst + 16 + klen, vlen, lane);
-  }
+  list_write_record(r, row, m, vlen, dd, spill, spill_used, heap, heap_used,
+                    arena, arena_cap, lane);
 }
 
 // ---- batched point read (kb_get_batch) ---------------------
@@ -2258,6 +2271,319 @@ __global__ __launch_bounds__(256) void k_wreg_emit(
   }
 }
 
+// ---- batched stream read (kb_stream_next_batch) ----------
+// A stream's next kvs, window by window (splan.h): k_stream_window cuts the
+// window, k_stream_mark ballots the winners of both segments across the chip
+// (the predicate of k_count_tiles), k_stream_plan scans the per-word counts,
+// k_stream_rank merges the two runs' winners by rank into the call's table,
+// k_stream_cut + k_stream_emit cut the table to the reply and write the wire
+// bytes into the arena. k_range_scan2 is not involved.
+//
+// sw = the window on the device: base rows [LO, E) of the segment [LO, HI),
+// delta rows [DLO, DHIW) of [DLO, DHI). sacc = {rows, tiles} the mark kernel
+// covered. shdr = StreamWinHdr, cres = StreamCut (slab_dev.h).
+constexpr int SW_LO = 0, SW_E = 1, SW_DLO = 2, SW_DHIW = 3, SW_HI = 4,
+              SW_DHI = 5, SW_N = 8;
+
+// one block. First window of a call (cont == 0): the four run bounds from the
+// stream's frontier, one wave each, as k_range_bounds. A later window starts
+// where the previous one ended. Wave 0 then cuts the base segment to W rows
+// and, when the window stops at base row e short of the bound, ends the delta
+// segment at the first delta row of key(e): the compare is rowcmp_q on a slab
+// row's key, spilled tail included.
+__global__ __launch_bounds__(256) void k_stream_window(
+    Run b, int64_t n, Run d, int64_t dn, const uint8_t* __restrict__ spill,
+    const uint8_t* __restrict__ qtails, const DevRangeQ* __restrict__ qs,
+    int cont, int64_t W, int64_t* __restrict__ sw,
+    unsigned long long* __restrict__ sacc) {
+  __shared__ int64_t bd[4];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (!cont) {
+    const DevRangeQ& Q = qs[0];
+    const QKey qstart{Q.start, Q.start_klen, Q.start_ko, qtails};
+    const QKey qend{Q.end, Q.end_klen, Q.end_ko, qtails};
+    int64_t r;
+    if (w == 0) r = d_lb_wave(b, spill, n, qstart, Q.start_rev);
+    else if (w == 1) r = d_lb_wave(b, spill, n, qend, 0);
+    else if (w == 2) r = d_lb_wave(d, spill, dn, qstart, Q.start_rev);
+    else r = d_lb_wave(d, spill, dn, qend, 0);
+    if (lane == 0) bd[w] = r;
+  } else if (threadIdx.x == 0) {
+    bd[0] = sw[SW_E];
+    bd[1] = sw[SW_HI];
+    bd[2] = sw[SW_DHIW];
+    bd[3] = sw[SW_DHI];
+  }
+  __syncthreads();
+  if (w != 0) return;  // wave 0 goes on whole: d_lb_wave needs all its lanes
+  const int64_t lo = kbstream::ClampLo(bd[0], n);
+  const int64_t hi = kbstream::ClampHi(lo, bd[1], n);
+  const int64_t dlo = kbstream::ClampLo(bd[2], dn);
+  const int64_t dhi = kbstream::ClampHi(dlo, bd[3], dn);
+  const int64_t e = kbstream::WindowEnd(lo, hi, W);
+  int64_t klb = dhi;
+  if (e < hi) klb = d_lb_wave(d, spill, dn, row_qk(b, spill, e), 0);
+  if (lane == 0) {
+    sw[SW_LO] = lo;
+    sw[SW_E] = e;
+    sw[SW_DLO] = dlo;
+    sw[SW_DHIW] = kbstream::DeltaEnd(e, hi, dlo, dhi, klb);
+    sw[SW_HI] = hi;
+    sw[SW_DHI] = dhi;
+    sacc[0] = 0;
+    sacc[1] = 0;
+  }
+}
+
+// fixed grid, blocks grid-stride over the tiles of both segments (splan.h).
+// A tile is 16 slices of 64 rows, four per wave; per slice one ballot word of
+// the winner predicate — rev / meta / shadow 8-byte streams, no key bytes, the
+// rev[i + 1] load guarded by the end of the SEGMENT (HI / DHI), not of the
+// tile or the window — with its winner count and the winners' wire bytes from
+// meta. Slice s of a segment is word s of that run's arrays (bw_cap / dw_cap
+// words; a slice past them is skipped and not counted as done).
+__global__ __launch_bounds__(256) void k_stream_mark(
+    Run b, Run d, int64_t dn, const uint64_t* __restrict__ shadow, uint64_t R,
+    int keys_only, const int64_t* __restrict__ sw,
+    uint64_t* __restrict__ bball, uint32_t* __restrict__ bcnt,
+    uint64_t* __restrict__ bbytes, int64_t bw_cap,
+    uint64_t* __restrict__ dball, uint32_t* __restrict__ dcnt,
+    uint64_t* __restrict__ dbytes, int64_t dw_cap,
+    unsigned long long* __restrict__ sacc) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t lo = sw[SW_LO], e = sw[SW_E], dlo = sw[SW_DLO],
+                dhiw = sw[SW_DHIW], hi = sw[SW_HI], dhi = sw[SW_DHI];
+  const uint64_t total = kbstream::SegTiles(e - lo) + kbstream::SegTiles(dhiw - dlo);
+  uint64_t rows_done = 0, tiles_done = 0;  // thread 0's tallies of this block
+  for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {
+    const kbstream::Tile tl = kbstream::MapTile(lo, e, dlo, dhiw, t);
+    const bool isd = tl.run != 0;
+    const int64_t seg_lo = isd ? dlo : lo, seg_hi = isd ? dhi : hi;
+    const int64_t wcap = isd ? dw_cap : bw_cap;
+    if (tl.r0 < seg_lo || tl.r0 >= tl.r1 || tl.r1 > seg_hi ||
+        ((tl.r1 - 1 - seg_lo) >> 6) >= wcap)
+      continue;  // block-uniform
+    const uint64_t* __restrict__ rev = isd ? d.rev : b.rev;
+    const uint64_t* __restrict__ meta = isd ? d.meta : b.meta;
+    const uint64_t* __restrict__ sh = (!isd && dn > 0) ? shadow : nullptr;
+    uint64_t* ball = isd ? dball : bball;
+    uint32_t* cnt = isd ? dcnt : bcnt;
+    uint64_t* bytes = isd ? dbytes : bbytes;
+    for (int64_t i0 = tl.r0 + ((int64_t)w << 6); i0 < tl.r1; i0 += 256) {
+      const int64_t i = i0 + lane;
+      bool win = false;
+      uint64_t sz = 0;
+      if (i < tl.r1) {
+        const uint64_t rv = rev[i], m = meta[i];
+        const uint64_t rvn = (i + 1 < seg_hi) ? rev[i + 1] : 0;
+        const uint64_t s = sh ? sh[i] : UINT64_MAX;
+        if (rv > 0 && rv <= R && !(m & M_TOMB) && !(s != UINT64_MAX && s <= R))
+          win = !(m & M_SAME_NEXT) || rvn > R;
+        if (win)
+          sz = kbstream::RecordBytes(meta_klen(m), keys_only ? 0 : meta_vlen(m));
+      }
+      const uint64_t bl = __ballot(win);
+#pragma unroll
+      for (int k = 32; k >= 1; k >>= 1) {
+        const uint32_t l = __shfl_xor((uint32_t)sz, k, 64);
+        const uint32_t h = __shfl_xor((uint32_t)(sz >> 32), k, 64);
+        sz += ((uint64_t)h << 32) | l;
+      }
+      if (lane == 0) {
+        const int64_t word = (i0 - seg_lo) >> 6;
+        ball[word] = bl;
+        cnt[word] = (uint32_t)__popcll(bl);
+        bytes[word] = sz;
+      }
+    }
+    if (threadIdx.x == 0) {
+      tiles_done += 1;
+      rows_done += (uint64_t)(tl.r1 - tl.r0);
+    }
+  }
+  if (threadIdx.x == 0 && tiles_done) {
+    atomicAdd(&sacc[0], (unsigned long long)rows_done);
+    atomicAdd(&sacc[1], (unsigned long long)tiles_done);
+  }
+}
+
+// one block: exclusive scans of the per-word winner counts of both segments
+// (wave scans chained through LDS, as k_count_plan) into bpfx / dpfx, each
+// with its total and an empty ballot word behind the last slice, so that a
+// rank lookup at the segment's end needs no special case; then the one small
+// header the host reads back per window.
+__global__ __launch_bounds__(256) void k_stream_plan(
+    const int64_t* __restrict__ sw, uint64_t* __restrict__ bball,
+    const uint32_t* __restrict__ bcnt, const uint64_t* __restrict__ bbytes,
+    uint32_t* __restrict__ bpfx, uint64_t* __restrict__ dball,
+    const uint32_t* __restrict__ dcnt, const uint64_t* __restrict__ dbytes,
+    uint32_t* __restrict__ dpfx, int64_t bw_cap, int64_t dw_cap,
+    const unsigned long long* __restrict__ sacc, uint64_t* __restrict__ shdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint64_t wsum[4], wbyt[4];
+  const int64_t brows = sw[SW_E] - sw[SW_LO], drows = sw[SW_DHIW] - sw[SW_DLO];
+  uint64_t wins[2], bytes_all = 0;
+  for (int run = 0; run < 2; ++run) {
+    const uint32_t* cnt = run ? dcnt : bcnt;
+    const uint64_t* byt = run ? dbytes : bbytes;
+    uint32_t* pfx = run ? dpfx : bpfx;
+    int64_t nw = kbstream::SegWords(run ? drows : brows);
+    if (nw > (run ? dw_cap : bw_cap)) nw = run ? dw_cap : bw_cap;
+    uint64_t base = 0;  // block-uniform running total
+    for (int64_t c0 = 0; c0 < nw; c0 += 256) {
+      const int64_t s = c0 + threadIdx.x;
+      const uint64_t c = s < nw ? cnt[s] : 0, y = s < nw ? byt[s] : 0;
+      const uint64_t incl = wp_scan64(c, lane), yincl = wp_scan64(y, lane);
+      if (lane == 63) { wsum[w] = incl; wbyt[w] = yincl; }
+      __syncthreads();
+      uint64_t woff = 0, tot = 0, ytot = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < w) woff += wsum[k];
+        tot += wsum[k];
+        ytot += wbyt[k];
+      }
+      if (s < nw) pfx[s] = (uint32_t)(base + woff + incl - c);
+      base += tot;
+      bytes_all += ytot;
+      __syncthreads();  // wsum / wbyt reused by the next pass
+    }
+    if (threadIdx.x == 0) {  // the arrays hold cap + 1 words
+      pfx[nw] = (uint32_t)base;
+      (run ? dball : bball)[nw] = 0;
+    }
+    wins[run] = base;
+  }
+  if (threadIdx.x == 0) {
+    const uint64_t rows = (uint64_t)(brows > 0 ? brows : 0) + (uint64_t)(drows > 0 ? drows : 0);
+    const uint64_t tiles = kbstream::SegTiles(brows) + kbstream::SegTiles(drows);
+    uint32_t flags = 0;
+    if (sw[SW_E] >= sw[SW_HI]) flags |= SWH_LAST;
+    if (sacc[0] == rows && sacc[1] == tiles) flags |= SWH_COVERED;
+    shdr[0] = wins[0] | (wins[1] << 32);
+    shdr[1] = sacc[0];
+    shdr[2] = bytes_all;
+    shdr[3] = (uint64_t)(uint32_t)sacc[1] | ((uint64_t)flags << 32);
+  }
+}
+
+// one wave per ballot word (base words first, then delta words), one lane per
+// row slot: a winner's index in its own run is the word prefix plus the
+// popcount of the lower ballot bits; its merged position adds the number of
+// the OTHER run's winners with a smaller key = a lower bound of (key, rev 0)
+// over that run's segment, turned into a winner count by that run's word
+// prefix and ballot. A key wins in one run only (shadow column), so there are
+// no ties. With no winner in the other run the position is the own index and
+// no key is compared. The tagged row and its wire size go to slot tcount +
+// position of the call's merged table, as far as tcap reaches.
+__global__ __launch_bounds__(256) void k_stream_rank(
+    Run b, Run d, const uint8_t* __restrict__ spill, int64_t n, int64_t dn,
+    const int64_t* __restrict__ sw, const uint64_t* __restrict__ bball,
+    const uint32_t* __restrict__ bpfx, const uint64_t* __restrict__ dball,
+    const uint32_t* __restrict__ dpfx, int64_t bw_cap, int64_t dw_cap,
+    const uint64_t* __restrict__ shdr, int keys_only, int64_t tcount,
+    int64_t tcap, uint64_t* __restrict__ mrows, uint64_t* __restrict__ msize) {
+  const int lane = threadIdx.x & 63;
+  const int64_t lo = sw[SW_LO], e = sw[SW_E], dlo = sw[SW_DLO], dhiw = sw[SW_DHIW];
+  int64_t nbw = kbstream::SegWords(e - lo), ndw = kbstream::SegWords(dhiw - dlo);
+  if (nbw > bw_cap) nbw = bw_cap;
+  if (ndw > dw_cap) ndw = dw_cap;
+  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= nbw + ndw) return;  // wave-uniform
+  const bool isd = g >= nbw;
+  const int64_t word = isd ? g - nbw : g;
+  const uint64_t bl = (isd ? dball : bball)[word];
+  if (!((bl >> lane) & 1)) return;  // no wave-wide operation follows
+  const int64_t row = (isd ? dlo : lo) + (word << 6) + lane;
+  if (row >= (isd ? dhiw : e) || row >= (isd ? dn : n)) return;
+  const Run& r = isd ? d : b;
+  int64_t pos = (int64_t)(isd ? dpfx : bpfx)[word] +
+                __popcll(bl & ((1ull << lane) - 1));
+  const uint64_t other = isd ? (shdr[0] & 0xffffffffull) : (shdr[0] >> 32);
+  if (other) {
+    const Run& o = isd ? b : d;
+    const int64_t olo = isd ? lo : dlo, ohi = isd ? e : dhiw;
+    const int64_t off = d_lb_range(o, spill, olo, ohi, row_qk(r, spill, row), 0) - olo;
+    const int64_t ow = off >> 6;  // <= the other run's word count
+    if (off < 0 || ow > (isd ? nbw : ndw)) return;
+    const uint64_t obl = (off & 63) ? (isd ? bball : dball)[ow] : 0;
+    pos += (int64_t)(isd ? bpfx : dpfx)[ow] +
+           __popcll(obl & ((1ull << (off & 63)) - 1));
+  }
+  const int64_t idx = tcount + pos;
+  if (idx < 0 || idx >= tcap) return;
+  const uint64_t m = r.meta[row];
+  mrows[idx] = (uint64_t)row | (isd ? ROW_TAG_DELTA : 0);
+  msize[idx] = kbstream::RecordBytes(meta_klen(m), keys_only ? 0 : meta_vlen(m));
+}
+
+// one block: exclusive byte prefix over the merged table's wire sizes (wave
+// scans chained through LDS) into moff, and the cut (splan.h Fits): the
+// records that fit max_kvs, the caller's buffer and the arena form a prefix,
+// so their number and bytes are plain sums over the fit flags.
+__global__ __launch_bounds__(256) void k_stream_cut(
+    const uint64_t* __restrict__ msize, int64_t ntab, uint64_t max_kvs,
+    uint64_t lim, uint64_t* __restrict__ moff, uint64_t* __restrict__ cres) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint64_t wsum[4], wfit[4], wfb[4];
+  uint64_t base = 0, nfit = 0, fbytes = 0;  // block-uniform running totals
+  for (int64_t c0 = 0; c0 < ntab; c0 += 256) {
+    const int64_t j = c0 + threadIdx.x;
+    const uint64_t sz = j < ntab ? msize[j] : 0;
+    const uint64_t incl = wp_scan64(sz, lane);
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint64_t woff = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < w) woff += wsum[k];
+      tot += wsum[k];
+    }
+    const uint64_t off = base + woff + incl - sz;
+    const bool fit = j < ntab && kbstream::Fits((uint64_t)j, off, sz, max_kvs, lim);
+    if (j < ntab) moff[j] = off;
+    const uint64_t fb = wp_scan64(fit ? sz : 0, lane);
+    const uint64_t fc = (uint64_t)__popcll(__ballot(fit));
+    if (lane == 63) { wfit[w] = fc; wfb[w] = fb; }
+    __syncthreads();  // also: wsum is free for the next pass
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { nfit += wfit[k]; fbytes += wfb[k]; }
+    base += tot;
+    __syncthreads();  // wfit / wfb reused by the next pass
+  }
+  if (threadIdx.x == 0) {
+    cres[0] = nfit;
+    cres[1] = fbytes;
+    cres[2] = 0;  // offset of the last record: k_stream_emit's wave n - 1
+    cres[3] = ntab > 0 ? msize[0] : 0;
+  }
+}
+
+// one wave per record of the cut, k_list_emit's record writer: key column
+// row, key-spill tail, value. The wave of the last record also leaves its
+// offset, where the host reads the stream's new frontier key.
+__global__ __launch_bounds__(256) void k_stream_emit(
+    Run rb, Run rd, int64_t n, int64_t dn,
+    const uint8_t* __restrict__ spill, int64_t spill_used,
+    const uint8_t* __restrict__ heap, int64_t heap_used,
+    const uint64_t* __restrict__ mrows, const uint64_t* __restrict__ moff,
+    int64_t ntab, int keys_only, uint64_t* __restrict__ cres,
+    uint8_t* __restrict__ arena, int64_t arena_cap) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= cres[0] || g >= (uint64_t)ntab) return;  // wave-uniform
+  const uint64_t rt = mrows[g];
+  const bool isd = (rt & ROW_TAG_DELTA) != 0;
+  const int64_t row = (int64_t)(rt & ROW_MASK);
+  if (row >= (isd ? dn : n)) return;
+  const Run& r = isd ? rd : rb;
+  const uint64_t m = r.meta[row];
+  const uint64_t dd = moff[g];
+  list_write_record(r, row, m, keys_only ? 0 : meta_vlen(m), dd, spill,
+                    spill_used, heap, heap_used, arena, arena_cap, lane);
+  if (g + 1 == cres[0] && lane == 0) cres[2] = dd;
+}
+
 // ------------------------------------------------------------------ Impl ---
 
 struct Slab::Impl {
@@ -2649,6 +2975,77 @@ struct Slab::Impl {
     return true;
   }
 
+  // batched stream read (allocated once at Create, sized from
+  // KB_STREAM_WINDOW, the delta capacity and KB_STREAM_MAX_KVS). Per run the
+  // ballot words with their counts, bytes and prefixes (one word more than
+  // the run can have slices), the merged table, the window state, the
+  // query of the frontier and the two read-back blocks.
+  int64_t stream_window = kbstream::kDefaultWindow;   // KB_STREAM_WINDOW
+  int64_t stream_max_kvs = kbstream::kDefaultMaxKvs;  // KB_STREAM_MAX_KVS
+  int64_t sbw_cap = 0, sdw_cap = 0;  // ballot words per run
+  uint64_t *d_sbball = nullptr, *d_sbbytes = nullptr, *d_sdball = nullptr,
+           *d_sdbytes = nullptr;
+  uint32_t *d_sbcnt = nullptr, *d_sbpfx = nullptr, *d_sdcnt = nullptr,
+           *d_sdpfx = nullptr;
+  uint64_t *d_smrows = nullptr, *d_smsize = nullptr, *d_smoff = nullptr;
+  int64_t* d_swin = nullptr;               // [SW_N]
+  unsigned long long* d_sacc = nullptr;    // [2]
+  uint64_t *d_shdr = nullptr, *h_shdr = nullptr;  // [4] window | [4] cut
+  DevRangeQ *d_sq = nullptr, *h_sq = nullptr;
+  uint8_t* d_stails = nullptr;
+  int64_t stails_cap = 0;
+  hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr, ev_s2 = nullptr;
+  void free_stream() {
+    for (void* q : {(void*)d_sbball, (void*)d_sbbytes, (void*)d_sdball,
+                    (void*)d_sdbytes, (void*)d_sbcnt, (void*)d_sbpfx,
+                    (void*)d_sdcnt, (void*)d_sdpfx, (void*)d_smrows,
+                    (void*)d_smsize, (void*)d_smoff, (void*)d_swin,
+                    (void*)d_sacc, (void*)d_shdr, (void*)d_sq, (void*)d_stails})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_shdr, (void*)h_sq})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_s0, ev_s1, ev_s2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  // Create only; a failure leaves what it got to free_stream
+  bool alloc_stream(std::string* err) {
+    HIP_CHECK(hipEventCreate(&ev_s0));
+    HIP_CHECK(hipEventCreate(&ev_s1));
+    HIP_CHECK(hipEventCreate(&ev_s2));
+    sbw_cap = kbstream::SegWords(std::min(stream_window, max_rows));
+    sdw_cap = kbstream::SegWords(delta_cap);
+    HIP_CHECK(hipMalloc(&d_sbball, (sbw_cap + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_sbbytes, (sbw_cap + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_sbcnt, (sbw_cap + 1) * 4));
+    HIP_CHECK(hipMalloc(&d_sbpfx, (sbw_cap + 1) * 4));
+    HIP_CHECK(hipMalloc(&d_sdball, (sdw_cap + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_sdbytes, (sdw_cap + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_sdcnt, (sdw_cap + 1) * 4));
+    HIP_CHECK(hipMalloc(&d_sdpfx, (sdw_cap + 1) * 4));
+    HIP_CHECK(hipMalloc(&d_smrows, stream_max_kvs * 8));
+    HIP_CHECK(hipMalloc(&d_smsize, stream_max_kvs * 8));
+    HIP_CHECK(hipMalloc(&d_smoff, stream_max_kvs * 8));
+    HIP_CHECK(hipMalloc(&d_swin, SW_N * 8));
+    HIP_CHECK(hipMalloc(&d_sacc, 16));
+    HIP_CHECK(hipMalloc(&d_sq, sizeof(DevRangeQ)));
+    HIP_CHECK(hipHostMalloc(&h_sq, sizeof(DevRangeQ)));
+    HIP_CHECK(hipHostMalloc(&h_shdr, 64));
+    HIP_CHECK(hipMalloc(&d_shdr, 64));
+    return ensure_stream_tails(0, err);
+  }
+  // the frontier query's key tails (keys > 96 B) grow with the longest seen
+  bool ensure_stream_tails(int64_t tail_bytes, std::string* err) {
+    if (tail_bytes > stails_cap || !d_stails) {
+      if (d_stails) (void)hipFree(d_stails);
+      d_stails = nullptr;
+      stails_cap = 0;
+      int64_t cap = tail_bytes * 2 + 4096;
+      HIP_CHECK(hipMalloc(&d_stails, cap));
+      stails_cap = cap;
+    }
+    return true;
+  }
+
   // KB_SCAN_DBG=1: per-phase wall_clock64 cycle sums from k_range_scan2
   // ([0]=bounds [1]=pass1a [2]=pass1b [3]=scatter [4]=merge [5]=block total)
   unsigned long long* d_dbg = nullptr;
@@ -2770,6 +3167,7 @@ struct Slab::Impl {
     free_list();
     free_getb();
     free_count();
+    free_stream();
     if (h_pack) (void)hipHostFree(h_pack);
     for (int i = 0; i < 2; ++i) {
       if (h_resmeta[i]) (void)hipHostFree(h_resmeta[i]);
@@ -3025,6 +3423,10 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   I->wreg_cfg_bytes = env_i64("KB_WATCH_REG_BYTES", kbwreg::kDefaultBytes);
   if (I->wreg_cfg_bytes < 8) I->wreg_cfg_bytes = 8;
   I->count_tile = kbcount::ClampTile(env_i64("KB_COUNT_TILE", kbcount::kDefaultTile));
+  I->stream_window = kbstream::ClampWindow(
+      env_i64("KB_STREAM_WINDOW", kbstream::kDefaultWindow));
+  I->stream_max_kvs = kbstream::ClampMaxKvs(
+      env_i64("KB_STREAM_MAX_KVS", kbstream::kDefaultMaxKvs));
   {
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
@@ -3143,6 +3545,7 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   HIP_CHECK_NULL(hipMalloc(&I->d_bounds, 256 * 8));
   HIP_CHECK_NULL(hipMalloc(&I->d_bkeys, 256 * KEYW));
   HIP_CHECK_NULL(hipMalloc(&I->d_brevs, 256 * 8));
+  if (!I->alloc_stream(err)) return nullptr;
   (void)fail;
   return s;
 }
@@ -3941,6 +4344,154 @@ bool Slab::CountBatchLaunch(const DevRangeQ* qs, int nq,
   perf.count_batch_tiles += (int64_t)h->tiles;
   perf.count_batch_rows += (int64_t)h->rows;
   *hdr = h;
+  return true;
+}
+
+// ---- batched stream read (kb_stream_next_batch) ---------------------------
+
+int64_t Slab::stream_window() const { return p->stream_window; }
+int64_t Slab::stream_max_kvs() const { return p->stream_max_kvs; }
+
+bool Slab::StreamWindowLaunch(const DevRangeQ& q, const std::string& qtails,
+                              bool cont, bool keys_only, int64_t tcount,
+                              int64_t tcap, const StreamWinHdr** hdr,
+                              std::string* err) {
+  Impl* I = p;
+  if (!I->ensure_stream_tails((int64_t)qtails.size(), err)) return false;
+  if (tcount < 0 || tcap < tcount || tcap > I->stream_max_kvs) {
+    if (err) *err = "stream batch: bad merged table span (KB_STREAM_MAX_KVS)";
+    return false;
+  }
+  I->last_nq = 0;  // the arena stops holding gathered records
+  if (!cont) {
+    memcpy(I->h_sq, &q, sizeof(DevRangeQ));
+    HIP_CHECK(hipMemcpyAsync(I->d_sq, I->h_sq, sizeof(DevRangeQ),
+                             hipMemcpyHostToDevice, I->stream));
+    if (!qtails.empty())
+      HIP_CHECK(hipMemcpyAsync(I->d_stails, qtails.data(), qtails.size(),
+                               hipMemcpyHostToDevice, I->stream));
+  }
+  const int ko = keys_only ? 1 : 0;
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  HIP_CHECK(hipEventRecord(I->ev_s0, I->stream));
+  hipLaunchKernelGGL(k_stream_window, dim3(1), dim3(256), 0, I->stream,
+                     I->A.run(), I->n, I->DA.run(), I->dn, I->spillA,
+                     I->d_stails, I->d_sq, cont ? 1 : 0, I->stream_window,
+                     I->d_swin, I->d_sacc);
+  HIP_CHECK(hipGetLastError());
+  // the window's extent is known only on the device: the mark grid is fixed,
+  // the rank grid covers the most words a window can have
+  const int64_t max_rows_w = std::min(I->stream_window, I->n);
+  const int64_t max_tiles = (int64_t)kbstream::SegTiles(max_rows_w) +
+                            (int64_t)kbstream::SegTiles(I->dn);
+  const int64_t mark_grid =
+      std::max<int64_t>(1, std::min<int64_t>(I->count_grid, max_tiles));
+  hipLaunchKernelGGL(k_stream_mark, dim3((uint32_t)mark_grid), dim3(256), 0,
+                     I->stream, I->A.run(), I->DA.run(), I->dn, I->shadow,
+                     q.read_rev, ko, I->d_swin, I->d_sbball, I->d_sbcnt,
+                     I->d_sbbytes, I->sbw_cap, I->d_sdball, I->d_sdcnt,
+                     I->d_sdbytes, I->sdw_cap, I->d_sacc);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(256), 0, I->stream,
+                     I->d_swin, I->d_sbball, I->d_sbcnt, I->d_sbbytes, I->d_sbpfx,
+                     I->d_sdball, I->d_sdcnt, I->d_sdbytes, I->d_sdpfx,
+                     I->sbw_cap, I->sdw_cap, I->d_sacc, I->d_shdr);
+  HIP_CHECK(hipGetLastError());
+  const int64_t max_words = kbstream::SegWords(max_rows_w) + kbstream::SegWords(I->dn);
+  if (max_words > 0 && tcap > tcount) {
+    hipLaunchKernelGGL(k_stream_rank, dim3((uint32_t)ceil_div(max_words, 4)),
+                       dim3(256), 0, I->stream, I->A.run(), I->DA.run(),
+                       I->spillA, I->n, I->dn, I->d_swin, I->d_sbball,
+                       I->d_sbpfx, I->d_sdball, I->d_sdpfx, I->sbw_cap,
+                       I->sdw_cap, I->d_shdr, ko, tcount, tcap, I->d_smrows,
+                       I->d_smsize);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(I->ev_s1, I->stream));
+  // the one small readback per window
+  HIP_CHECK(hipMemcpyAsync(I->h_shdr, I->d_shdr, sizeof(StreamWinHdr),
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_s2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_s0, I->ev_s1);
+  perf.stream_batch_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_s1, I->ev_s2);
+  perf.stream_batch_d2h_ms += ms;
+  const StreamWinHdr* h = (const StreamWinHdr*)I->h_shdr;
+  if (!(h->flags & SWH_COVERED)) {
+    if (err) *err = "stream batch: the mark kernel did not cover the window";
+    return false;
+  }
+  perf.stream_batch_windows++;
+  perf.stream_batch_rows += (int64_t)h->rows;
+  *hdr = h;
+  return true;
+}
+
+bool Slab::StreamCutEmit(int64_t ntab, int64_t max_kvs, uint64_t lim,
+                         bool keys_only, const StreamCut** cut,
+                         std::string* err) {
+  Impl* I = p;
+  if (!I->d_shdr || ntab < 0 || ntab > I->stream_max_kvs || max_kvs < 1) {
+    if (err) *err = "stream batch: no scanned window or bad table size";
+    return false;
+  }
+  if (lim > (uint64_t)I->arena_bytes) lim = (uint64_t)I->arena_bytes;
+  uint64_t* d_cres = I->d_shdr + 4;
+  (void)hipGetLastError();
+  HIP_CHECK(hipEventRecord(I->ev_s0, I->stream));
+  hipLaunchKernelGGL(k_stream_cut, dim3(1), dim3(256), 0, I->stream,
+                     I->d_smsize, ntab, (uint64_t)max_kvs, lim, I->d_smoff,
+                     d_cres);
+  HIP_CHECK(hipGetLastError());
+  const int64_t most = std::min(ntab, max_kvs);
+  if (most > 0) {
+    hipLaunchKernelGGL(k_stream_emit, dim3((uint32_t)ceil_div(most, 4)),
+                       dim3(256), 0, I->stream, I->A.run(), I->DA.run(), I->n,
+                       I->dn, I->spillA, I->spill_used_, I->heapA,
+                       I->heap_used_, I->d_smrows, I->d_smoff, ntab,
+                       keys_only ? 1 : 0, d_cres, I->d_gbuf, I->arena_bytes);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(I->ev_s1, I->stream));
+  HIP_CHECK(hipMemcpyAsync(I->h_shdr + 4, d_cres, sizeof(StreamCut),
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_s2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_s0, I->ev_s1);
+  perf.stream_batch_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_s1, I->ev_s2);
+  perf.stream_batch_d2h_ms += ms;
+  const StreamCut* c = (const StreamCut*)(I->h_shdr + 4);
+  if (c->n > (uint64_t)most || c->bytes > lim ||
+      (c->n > 0 && c->last_off >= c->bytes)) {
+    if (err) *err = "stream batch: the cut left its bounds";
+    return false;
+  }
+  *cut = c;
+  return true;
+}
+
+bool Slab::StreamFetch(int64_t bytes, uint8_t* reply, int64_t reply_off,
+                       std::string* err) {
+  Impl* I = p;
+  if (bytes <= 0 || bytes > I->arena_bytes || reply != I->h_lreply ||
+      reply_off < 0 || reply_off + bytes > I->lreply_cap) {
+    if (err) *err = "stream batch: bad fetch span";
+    return false;
+  }
+  HIP_CHECK(hipEventRecord(I->ev_s1, I->stream));
+  HIP_CHECK(hipMemcpyAsync(reply + reply_off, I->d_gbuf, bytes,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_s2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_s1, I->ev_s2);
+  perf.stream_batch_d2h_ms += ms;
   return true;
 }
 

@@ -147,6 +147,12 @@ struct Perf {
   double count_ms = 0, count_d2h_ms = 0;
   int64_t count_batch_calls = 0, count_batch_q = 0, count_batch_launches = 0,
           count_batch_tiles = 0, count_batch_rows = 0;
+  // batched stream read (kb_stream_next_batch): time in the k_stream_*
+  // kernels, the header and reply D2H, calls, windows scanned, rows the mark
+  // kernel covered, kvs returned, records served by the host fallback
+  double stream_batch_ms = 0, stream_batch_d2h_ms = 0;
+  int64_t stream_batch_calls = 0, stream_batch_windows = 0,
+          stream_batch_rows = 0, stream_batch_kvs = 0, stream_batch_host = 0;
   // which mergeRuns branch ran (k_merge_small / k_delta_rank + k_delta_scatter /
   // k_merge_rank_inv_big / the n == 0 scatter), delta appends that took the
   // async no-sync branch, and delta->base folds: the tests prove with these
@@ -203,6 +209,23 @@ struct CountBatchHdr {
   uint64_t tiles, rows, tiles_planned, rows_planned;
   uint64_t count[1];  // nq entries
 };
+// batched stream read (kb_stream_next_batch): what
+// k_stream_plan leaves per window and k_stream_cut / k_stream_emit per call
+struct StreamWinHdr {
+  uint32_t base_winners, delta_winners;
+  uint64_t rows;   // rows k_stream_mark covered
+  uint64_t bytes;  // wire bytes of the window's winners
+  uint32_t tiles, flags;  // SWH_*
+};
+constexpr uint32_t SWH_LAST = 1;     // the window reached the end of the range
+constexpr uint32_t SWH_COVERED = 2;  // the mark kernel covered the whole window
+struct StreamCut {
+  uint64_t n, bytes;   // records of the reply and their wire bytes
+  uint64_t last_off;   // arena offset of record n - 1
+  uint64_t first_size; // wire bytes of the table's first record (KB_ENOBUF)
+};
+static_assert(sizeof(StreamWinHdr) == 32 && sizeof(StreamCut) == 32,
+              "stream read-back layout");
 // batched watch registration (kb_watch_batch): one entry of a
 // sub-batch as the host stages it, and what k_wreg_plan leaves per watcher
 struct WregEntry {
@@ -393,6 +416,29 @@ class Slab {
   bool CountBatchLaunch(const DevRangeQ* qs, int nq, const std::string& qtails,
                         const CountBatchHdr** hdr, std::string* err);
   int64_t count_tile() const;  // KB_COUNT_TILE: rows per tile
+
+  // batched stream read (kb_stream_next_batch).
+  // StreamWindowLaunch scans one window: k_stream_window (cont = false: from
+  // the frontier bound in q, start_rev as for a chunked List; cont = true:
+  // from where the previous window of this call ended), k_stream_mark,
+  // k_stream_plan and k_stream_rank, which appends the window's winners in
+  // key order to the call's merged table from slot tcount on, up to tcap <=
+  // stream_max_kvs(). One 32-byte read-back; *hdr points into pinned memory
+  // valid until the next call. StreamCutEmit cuts the first ntab table
+  // entries to max_kvs records and lim wire bytes (k_stream_cut), writes them
+  // into the arena from offset 0 (k_stream_emit) and reads back 32 bytes.
+  // StreamFetch brings arena [0, bytes) to reply + reply_off (the pinned
+  // buffer of ListReply) with one D2H.
+  int64_t stream_window() const;   // KB_STREAM_WINDOW: base rows per window
+  int64_t stream_max_kvs() const;  // KB_STREAM_MAX_KVS: merged table entries
+  bool StreamWindowLaunch(const DevRangeQ& q, const std::string& qtails,
+                          bool cont, bool keys_only, int64_t tcount,
+                          int64_t tcap, const StreamWinHdr** hdr,
+                          std::string* err);
+  bool StreamCutEmit(int64_t ntab, int64_t max_kvs, uint64_t lim,
+                     bool keys_only, const StreamCut** cut, std::string* err);
+  bool StreamFetch(int64_t bytes, uint8_t* reply, int64_t reply_off,
+                   std::string* err);
 
   // compaction mark+sweep over encoded borders (compact.go:55-68 +
   // scanner.go:444-491, 566-591). Bounds are (key96, rev) pairs.

@@ -71,6 +71,8 @@ static void setBound(uint8_t dst96[KEYW], uint32_t* klen, uint64_t* ko,
   }
 }
 
+static void copyReply(uint8_t* dst, const uint8_t* src, size_t n);  // below
+
 static int64_t env_i64(const char* name, int64_t dflt) {
   const char* v = getenv(name);
   return v && *v ? atoll(v) : dflt;
@@ -440,6 +442,135 @@ Status Store::StreamNext(int64_t sid, std::vector<KeyValue>* kvs) {
     if (!more || r.recs.empty()) { ss.done = true; break; }
   }
   if (kvs->empty()) streams_.erase(it);  // empty == end marker now
+  return OK;
+}
+
+// kb_stream_next_batch: windows of the stream's range are
+// scanned one after another under one mutex hold until the merged table holds
+// max_kvs winners, their wire bytes fill the reply's budget, or the range
+// ends; a window without winners never ends the call unless it is the last.
+// The cut and the wire bytes come from the device; the frontier becomes the
+// last emitted key, read from the reply. Rows of the last window behind the
+// cut are scanned again by the next call, nothing else is.
+Status Store::StreamNextBatch(int64_t sid, int64_t max_kvs, int flags,
+                              uint8_t* out, size_t cap, size_t* out_len,
+                              uint64_t* n_kvs, int* more, std::string* errp) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  *out_len = 0;
+  if (n_kvs) *n_kvs = 0;
+  if (more) *more = 0;
+  if ((flags & ~1) != 0) return INVALID_ARG;
+  auto it = streams_.find(sid);
+  if (it == streams_.end()) return INVALID_ARG;
+  std::string errl;
+  std::string& err = errp ? *errp : errl;
+  const uint32_t zero = 0;
+  auto endMarker = [&]() {  // u32 0; the caller's buffer must hold it
+    *out_len = 4;
+    if (cap < 4) return NOBUF;
+    memcpy(out, &zero, 4);
+    streams_.erase(it);
+    return OK;
+  };
+  kbslab::Perf& perf = slab_->perf;
+  perf.stream_batch_calls++;
+  if (it->second.done) return endMarker();
+  if (!syncReads(&err)) return INTERNAL;
+  StreamState& ss = it->second;
+  Status cst = checkCompactRace(ss.read_rev);
+  if (cst != OK) { streams_.erase(it); return cst; }
+  const bool konly = (flags & 1) != 0;
+  const int64_t maxn = kbstream::ResolveMaxKvs(max_kvs, slab_->stream_max_kvs());
+  const uint64_t arena = (uint64_t)slab_->arena_bytes();
+  const uint64_t lim = kbstream::CutLimit(cap, arena);
+
+  DevRangeQ q{};
+  std::string qtails;
+  setBound(q.start, &q.start_klen, &q.start_ko, ss.frontier, &qtails);
+  setBound(q.end, &q.end_klen, &q.end_ko, ss.end, &qtails);
+  q.read_rev = ss.read_rev;
+  q.start_rev = ss.started ? UINT64_MAX : 0;
+  q.keys_only = konly ? 1 : 0;
+  int64_t winners = 0;   // of the windows scanned so far, whether tabled or not
+  uint64_t wbytes = 0;   // their wire bytes
+  bool last = false;
+  for (bool cont = false; !last; cont = true) {
+    const kbslab::StreamWinHdr* h = nullptr;
+    if (!slab_->StreamWindowLaunch(q, qtails, cont, konly,
+                                   std::min(winners, maxn), maxn, &h, &err))
+      return INTERNAL;
+    winners += (int64_t)h->base_winners + (int64_t)h->delta_winners;
+    wbytes += h->bytes;
+    last = (h->flags & kbslab::SWH_LAST) != 0;
+    if (winners >= maxn || (winners > 0 && wbytes >= lim)) break;
+  }
+  slab_->ForgetLastRange();
+  if (winners == 0) return endMarker();  // the range held nothing more
+
+  const int64_t ntab = std::min(winners, maxn);
+  const kbslab::StreamCut* cut = nullptr;
+  if (!slab_->StreamCutEmit(ntab, maxn, lim, konly, &cut, &err)) return INTERNAL;
+  if (cut->n == 0) {
+    if (cap < 4 || cut->first_size > (uint64_t)cap - 4) {
+      *out_len = (size_t)kbstream::EnobufSize(cut->first_size);
+      return NOBUF;  // nothing written, the stream unchanged
+    }
+    // one record larger than the arena: StreamNext's own path serves it
+    std::vector<kbslab::RangeResult> outs;
+    DevRangeQ q1 = q;
+    q1.cap = 1;
+    q1.keys_only = 0;
+    if (!slab_->RangeBatch({q1}, true, &outs, &err, qtails)) return INTERNAL;
+    slab_->ForgetLastRange();
+    if (outs[0].overflow || outs[0].recs.size() != 1) {
+      // kb_stream_next cannot hold it either; the stream stays unchanged
+      *out_len = (size_t)kbstream::EnobufSize(cut->first_size);
+      return NOBUF;
+    }
+    const kbslab::RangeResult::Rec& rec = outs[0].recs[0];
+    const size_t vl = konly ? 0 : rec.val.size();
+    if (kblist::RecordSize(rec.key.size(), vl) != cut->first_size) {
+      err = "stream batch: the host path found another record";
+      return INTERNAL;
+    }
+    const uint32_t one = 1;
+    memcpy(out, &one, 4);
+    kblist::PutRecord(out + 4, rec.rev, rec.key.data(), (uint32_t)rec.key.size(),
+                      rec.val.data(), (uint32_t)vl);
+    *out_len = 4 + (size_t)cut->first_size;
+    ss.frontier = rec.key;
+    ss.started = true;
+    ss.done = last && winners == 1;
+    if (more) *more = ss.done ? 0 : 1;
+    if (n_kvs) *n_kvs = 1;
+    perf.stream_batch_host++;
+    perf.stream_batch_kvs++;
+    ops_range_++;
+    return OK;
+  }
+  const size_t total = 4 + (size_t)cut->bytes;
+  uint8_t* reply = slab_->ListReply((int64_t)total, &err);
+  if (!reply) return INTERNAL;
+  if (!slab_->StreamFetch((int64_t)cut->bytes, reply, 4, &err)) return INTERNAL;
+  const uint32_t n32 = (uint32_t)cut->n;
+  memcpy(reply, &n32, 4);
+  // the new frontier: the key of the last record
+  const uint8_t* lr = reply + 4 + cut->last_off;
+  uint32_t klen = 0;
+  memcpy(&klen, lr + 8, 4);
+  if (cut->last_off + 12 + (uint64_t)klen > cut->bytes) {
+    err = "stream batch: the last record leaves the reply";
+    return INTERNAL;
+  }
+  ss.frontier.assign((const char*)lr + 12, klen);
+  ss.started = true;
+  ss.done = last && (int64_t)cut->n == winners;
+  copyReply(out, reply, total);
+  *out_len = total;
+  if (more) *more = ss.done ? 0 : 1;
+  if (n_kvs) *n_kvs = cut->n;
+  perf.stream_batch_kvs += (int64_t)cut->n;
+  ops_range_++;
   return OK;
 }
 
@@ -2646,6 +2777,17 @@ std::string Store::PerfJson() {
            (long long)p.wreg_watchers_host,
            (long long)p.wreg_watchers_nocatchup,
            (long long)p.wreg_events_scanned, (long long)p.wreg_refs, p.wreg_ms);
+  // kb_stream_next_batch: 173 fixed characters, 5 integers and 2 floats more,
+  // i.e. 2688 + 173 + 7 * 20 = 3001 characters at worst: under the buffer
+  at += snprintf(buf + at, sizeof(buf) - (size_t)at,
+           "\"stream_batch_calls\":%lld,\"stream_batch_windows\":%lld,"
+           "\"stream_batch_rows\":%lld,\"stream_batch_kvs\":%lld,"
+           "\"stream_batch_host\":%lld,\"stream_batch_ms\":%.3f,"
+           "\"stream_batch_d2h_ms\":%.3f,",
+           (long long)p.stream_batch_calls, (long long)p.stream_batch_windows,
+           (long long)p.stream_batch_rows, (long long)p.stream_batch_kvs,
+           (long long)p.stream_batch_host, p.stream_batch_ms,
+           p.stream_batch_d2h_ms);
   snprintf(buf + at, sizeof(buf) - (size_t)at,
            "\"wpoll_ms\":%.3f,\"wpoll_d2h_ms\":%.3f,\"wpoll_launches\":%lld,"
            "\"wpoll_events_dev\":%lld,\"wpoll_events_host\":%lld,"

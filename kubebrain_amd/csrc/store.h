@@ -22,6 +22,7 @@
 #include "gplan.h"
 #include "lplan.h"
 #include "slab_dev.h"
+#include "splan.h"
 #include "wpoll.h"
 #include "wreg.h"
 
@@ -112,6 +113,15 @@ class Store {
   // fills kvs with the next batch (<=300); empty batch == end marker (stream
   // closes itself)
   Status StreamNext(int64_t sid, std::vector<KeyValue>* kvs);
+  // batched stream read (kb_stream_next_batch): the next kvs of the stream
+  // in the kb_list wire, found, merged and serialized on the device window by
+  // window. Advances the same StreamState as StreamNext, so
+  // the two may alternate on one stream. flags bit 0 = keys_only. NOBUF
+  // writes nothing and leaves the stream unchanged (*out_len = 4 + the next
+  // record's size).
+  Status StreamNextBatch(int64_t sid, int64_t max_kvs, int flags, uint8_t* out,
+                         size_t cap, size_t* out_len, uint64_t* n_kvs,
+                         int* more, std::string* err = nullptr);
   void StreamClose(int64_t sid);
   // GetPartitions (range.go:208-245; single partition like badger.go:52-54)
   std::vector<Bytes> GetPartitions(const Bytes& start, const Bytes& end,
