@@ -218,6 +218,61 @@ int kb_test_count_plan(const long long* bounds, size_t nq, long long tile,
                        long long* t_r0, long long* t_r1, size_t tile_cap,
                        size_t* n_tiles);
 
+/* Range digest: per range the number, key bytes, value bytes and hash sum of
+ * the kvs an unbounded kb_list(start, end, rev) returns, computed where the
+ * data lives — the equivalent of etcd's HashKV(rev) per range, for comparing
+ * replicas, shards or a rebuilt slab without shipping the kvs to the host.
+ * qbuf = the blob kb_count_batch / kb_list_batch take: n x {u32 slen; u32
+ * elen; u64 rev; i64 limit; start; end}. limit is ignored, rev == 0 means
+ * latest.
+ * out = u32 n; n x {i32 status; i32 0; u64 header_rev; u64 count; u64
+ * key_bytes; u64 value_bytes; u64 hash} = 4 + 48 n bytes. header_rev is the
+ * committed revision at the call, the same in every entry. Status and
+ * validation per entry are exactly kb_count_batch's for the same query and
+ * rev (its validation of both bounds, the compaction check against the read
+ * revision); start >= end is KB_OK with an all-zero entry; a non-OK entry is
+ * all zero and never fails the call. enable_etcd_compatibility has no effect:
+ * the digest is defined by kb_list, not by the reference's Count. For a KB_OK
+ * entry: count = the number of those kvs, key_bytes = sum of klen,
+ * value_bytes = sum of vlen (also under keys_only), hash = sum of the record
+ * hashes mod 2^64 (0 for an empty range).
+ *
+ * The record hash, all arithmetic mod 2^64:
+ *   fmix(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ *            x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ *   G  = 0x9E3779B97F4A7C15   SK = 0x243F6A8885A308D3
+ *   SV = 0x13198A2E03707344   S1 = 0xA4093822299F31D0
+ *   S2 = 0x082EFA98EC4E6C89
+ *   For a byte string b of length L: word j (0 <= j < ceil(L / 8)) is bytes
+ *   [8j, 8j + 8) as a little-endian u64, bytes at or past L are zero;
+ *   piece(b, S) = sum_j fmix(word_j ^ (S + (j + 1) * G)); empty string: 0.
+ *   record = fmix(fmix(rev ^ S1) + fmix(((klen << 32) | vlen') ^ S2)
+ *                 + piece(key, SK) + piece(val', SV))
+ *   with vlen' = vlen and val' = val, or 0 and empty under keys_only.
+ * This is a multiset hash for detecting divergence and corruption, not an
+ * adversarial one: do not use it where an attacker chooses the records.
+ *
+ * flags bit 0 = keys_only: the hash covers rev, klen and the key only, the
+ * value heap is never read, value_bytes stays real. Any other bit is
+ * KB_EINVALID. KB_ENOBUF (cap < 4 + 48 n) is decided before any kernel runs:
+ * *out_len = required size, nothing is written. n == 0 is valid; n above
+ * KB_MAX_Q is served in sub-batches inside the call. *total_kvs = sum of the
+ * counts.
+ * Every range is cut into tiles of KB_DIGEST_TILE rows (a multiple of 64, at
+ * least 64, default 1024) that HIP kernels reduce across the whole chip
+ * (DESIGN.md §3.11). One mutex hold; a pending pipelined kb_bench_step batch
+ * is collected first. The call writes neither the winner tables nor the
+ * gather arena: kb_test_last_range returns after it exactly the bytes it
+ * returned before it. */
+int kb_digest_batch(kb_store*, const uint8_t* qbuf, size_t n, int flags,
+                    uint8_t* out, size_t cap, size_t* out_len,
+                    unsigned long long* total_kvs);
+/* TEST-ONLY, no GPU, no store: the host build of the record hash above
+ * (kdigest.h). flags bit 0 = keys_only. */
+unsigned long long kb_test_digest_record(unsigned long long rev,
+        const uint8_t* key, size_t klen, const uint8_t* val, size_t vlen,
+        int flags);
+
 /* ---- compaction (compact.go:31-127 + scanner.go:444-491,566-591) ---- */
 int kb_compact(kb_store*, uint64_t rev, uint64_t* out_rev);
 

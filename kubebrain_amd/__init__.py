@@ -23,7 +23,7 @@ def build(force: bool = False) -> str:
                                                "comm.cc", "slab_dev.h", "store.h",
                                                "wpoll.h", "lplan.h", "gplan.h",
                                                "stepstage.h", "dmerge.h", "cplan.h",
-                                               "wreg.h", "splan.h")]
+                                               "wreg.h", "splan.h", "kdigest.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "kb_slab.h"))
     stale = force or not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

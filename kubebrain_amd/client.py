@@ -89,6 +89,19 @@ def _parse_events(buf: bytes):
     return evs
 
 
+def record_digest(rev: int, key: bytes, val: bytes, keys_only: bool = False) -> int:
+    """The record hash kb_digest_batch sums per range (include/kb_slab.h),
+    computed on the host by the product library (kb_test_digest_record; needs
+    no GPU and no store)."""
+    from . import load_library
+
+    f = load_library().kb_test_digest_record
+    f.restype = C.c_ulonglong
+    f.argtypes = [C.c_ulonglong, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
+                  C.c_int]
+    return f(rev, key, len(key), val, len(val), 1 if keys_only else 0)
+
+
 class Store:
     """One API over both backends. prefix='okb_' (oracle) or 'kb_' (product)."""
 
@@ -288,6 +301,39 @@ class Store:
             st, _z, hr, c = struct.unpack_from("<iiQQ", raw, 4 + 24 * i)
             res.append((st, hr, c))
         assert sum(c for _, _, c in res) == total.value
+        return rc, res, raw
+
+    def digest_batch(self, queries, keys_only: bool = False):
+        """Range digests in one call (kb_digest_batch; product ABI only).
+        queries = [(start, end, rev, limit), ...] as for count_batch. Returns
+        (rc, [(status, header_rev, count, key_bytes, value_bytes, hash), ...],
+        raw_reply) in query order: per KB_OK entry the number, key bytes, value
+        bytes and sum of record_digest() of the kvs an unbounded list(start,
+        end, rev) returns. KB_ENOBUF is handled here by growing the buffer and
+        repeating the call (the failed attempt wrote nothing)."""
+        n = len(queries)
+        qbuf = self.encode_queries(queries)
+        out_len = C.c_size_t(); total = C.c_ulonglong()
+        f = self._f("digest_batch")
+        buf, cap = self.buf, self.BUF
+        for _ in range(4):
+            rc = f(C.c_void_p(self.h), qbuf, C.c_size_t(n),
+                   C.c_int(1 if keys_only else 0), buf, C.c_size_t(cap),
+                   C.byref(out_len), C.byref(total))
+            if rc != ENOBUF:
+                break
+            cap = out_len.value
+            buf = C.create_string_buffer(cap)
+        if rc != OK:
+            return rc, [], b""
+        raw = C.string_at(buf, out_len.value)
+        (cnt,) = struct.unpack_from("<I", raw, 0)
+        assert cnt == n and len(raw) == 4 + 48 * n, (cnt, n, len(raw))
+        res = []
+        for i in range(n):
+            st, _z, hr, c, kb, vb, h = struct.unpack_from("<iiQQQQQ", raw, 4 + 48 * i)
+            res.append((st, hr, c, kb, vb, h))
+        assert sum(r[2] for r in res) == total.value
         return rc, res, raw
 
     def compact(self, rev: int = 0):

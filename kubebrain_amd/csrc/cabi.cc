@@ -10,6 +10,7 @@
 
 #include "../../include/kb_slab.h"
 #include "cplan.h"
+#include "kdigest.h"
 #include "store.h"
 
 using kbstore::Bytes;
@@ -307,6 +308,28 @@ int kb_test_count_plan(const long long* bounds, size_t nq, long long tile,
     if (t_r1) t_r1[t] = tl.r1;
   }
   return KB_OK;
+}
+
+int kb_digest_batch(kb_store* h, const uint8_t* qbuf, size_t n, int flags,
+                    uint8_t* out, size_t cap, size_t* out_len,
+                    unsigned long long* total_kvs) {
+  std::string err;
+  size_t len = 0;
+  uint64_t total = 0;
+  Status st = ((Store*)h)->DigestBatch(qbuf, n, flags, out, cap, &len, &total,
+                                       &err);
+  if (out_len) *out_len = len;
+  if (total_kvs) *total_kvs = total;
+  if (st == kbstore::NOBUF) return KB_ENOBUF;
+  if (st == kbstore::INTERNAL) set_err(KB_EINTERNAL, err);
+  return st;
+}
+
+unsigned long long kb_test_digest_record(unsigned long long rev,
+                                         const uint8_t* key, size_t klen,
+                                         const uint8_t* val, size_t vlen,
+                                         int flags) {
+  return kbdigest::Record(rev, key, klen, val, vlen, (flags & 1) != 0);
 }
 
 int kb_compact(kb_store* h, uint64_t rev, uint64_t* out_rev) {

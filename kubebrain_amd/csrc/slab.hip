@@ -13,6 +13,7 @@
 
 #include "cplan.h"
 #include "dmerge.h"
+#include "kdigest.h"
 #include "slab_dev.h"
 #include "splan.h"
 #include "stepstage.h"
@@ -1969,6 +1970,282 @@ __global__ __launch_bounds__(256) void k_count_tiles(
   }
 }
 
+// ---- range digest (kb_digest_batch) -------------------------
+// Per query the number of winners, their key and value bytes and the sum of
+// their record hashes (kdigest.h). A sum of per-record hashes commutes, so a
+// digest is a tiled reduction like the count, but every winner's key and
+// value bytes are read: k_range_bounds (unchanged) -> k_digest_plan ->
+// k_digest_tiles. Nothing is written but the launch's own header.
+//
+// dhdr = {u64 tiles done; u64 rows done; u64 tiles planned; u64 rows planned;
+// u64 records skipped; nq x {u64 count; u64 key_bytes; u64 value_bytes; u64
+// hash}}: the block the host reads back.
+constexpr int DIGEST_HDR = 5;
+constexpr int DIGEST_VR = 2;  // value group steps (256 B each) requested ahead
+
+// k_count_plan's scan with the digest's header: the sums k_digest_tiles adds
+// to are zeroed here, one launch ahead of their first increment.
+__global__ __launch_bounds__(256) void k_digest_plan(
+    const int64_t* __restrict__ bounds, int nq, int64_t T,
+    uint64_t* __restrict__ pfx, uint64_t* __restrict__ dhdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nseg = 2 * nq;
+  __shared__ uint64_t wsum[4], wrows[4];
+  uint64_t base = 0, rows_all = 0;  // block-uniform running totals
+  for (int c0 = 0; c0 < nseg; c0 += 256) {
+    const int s = c0 + threadIdx.x;
+    uint64_t tiles = 0, rows = 0;
+    if (s < nseg) {
+      const int64_t lo = kbcount::SegLo(bounds, s), hi = kbcount::SegHi(bounds, s);
+      tiles = kbcount::SegTiles(lo, hi, T);
+      rows = (uint64_t)kbcount::SegRows(lo, hi);
+    }
+    const uint64_t incl = wp_scan64(tiles, lane);
+    const uint64_t rincl = wp_scan64(rows, lane);
+    if (lane == 63) { wsum[w] = incl; wrows[w] = rincl; }
+    __syncthreads();
+    uint64_t woff = 0, tot = 0, rtot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < w) woff += wsum[k];
+      tot += wsum[k];
+      rtot += wrows[k];
+    }
+    if (s < nseg) pfx[s] = base + woff + incl - tiles;
+    base += tot;
+    rows_all += rtot;
+    __syncthreads();  // wsum / wrows reused by the next pass
+  }
+  for (int e = threadIdx.x; e < 4 * nq; e += 256) dhdr[DIGEST_HDR + e] = 0;
+  if (threadIdx.x == 0) {
+    pfx[nseg] = base;
+    dhdr[0] = 0;
+    dhdr[1] = 0;
+    dhdr[2] = base;
+    dhdr[3] = rows_all;
+    dhdr[4] = 0;
+  }
+}
+
+// what one 16-lane group holds of one winner between the request of its
+// bytes and their mixing; every field but kv / vv is group-uniform
+struct DigestRec {
+  uint64_t rev, vo, ko;
+  uint32_t klen, vlen;  // vlen as meta has it, also under keys_only
+  uint32_t state;       // 0 none, 1 hash it, 2 unsafe source: skip and count
+  u32x4 kv;             // vector gl of the 96 B key column row (lanes 0-5)
+  u32x4 vv[DIGEST_VR];  // value vectors gl + 16 t
+};
+
+__device__ __forceinline__ uint64_t digest_u64(uint32_t lo, uint32_t hi) {
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// requests a winner's bytes without using them: the row's words (the same
+// address in all 16 lanes: one broadcast load each), then the key row's six
+// vectors on lanes 0-5, cut at ceil(klen / 8) words, and the first DIGEST_VR
+// group steps of the value. A source that is not 16-aligned or whose padded
+// extent leaves the used heap is not touched (state 2).
+__device__ __forceinline__ void digest_load(
+    const Run& r, int64_t row, bool konly, const uint8_t* __restrict__ heap,
+    uint64_t heap_used, uint64_t spill_used, uint32_t gl, DigestRec& c) {
+  const uint64_t m = r.meta[row];
+  c.rev = r.rev[row];
+  c.klen = meta_klen(m);
+  c.vlen = meta_vlen(m);
+  c.vo = 0;
+  c.ko = 0;
+  c.kv = u32x4{0, 0, 0, 0};
+#pragma unroll
+  for (int t = 0; t < DIGEST_VR; ++t) c.vv[t] = u32x4{0, 0, 0, 0};
+  const uint32_t hv = konly ? 0 : c.vlen;  // value bytes the hash covers
+  bool ok = true;
+  if (hv) {
+    c.vo = r.vo[row];
+    ok = (c.vo & 15) == 0 && c.vo <= heap_used &&
+         (((uint64_t)hv + 15) & ~15ull) <= heap_used - c.vo;
+  }
+  if (c.klen > (uint32_t)KEYW) {
+    c.ko = r.ko[row];
+    ok = ok && (c.ko & 15) == 0 && c.ko <= spill_used &&
+         (((uint64_t)c.klen - KEYW + 15) & ~15ull) <= spill_used - c.ko;
+  }
+  c.state = ok ? 1 : 2;
+  if (!ok) return;
+  const uint32_t kin = c.klen > (uint32_t)KEYW ? (uint32_t)KEYW : c.klen;
+  if (gl * 16 < kin) c.kv = ((const u32x4*)(r.keys + row * KEYW))[gl];
+#pragma unroll
+  for (int t = 0; t < DIGEST_VR; ++t) {
+    const uint32_t v = gl + 16 * t;
+    if (v * 16 < hv) c.vv[t] = ((const u32x4*)(heap + c.vo))[v];
+  }
+}
+
+// this lane's share of the record's word terms: its vector of the key row,
+// its vectors of the value (the requested ones, then whatever a long value
+// has left, 16 vectors per group step), its vectors of the key's spill tail,
+// whose word index continues at 12. The last partial word is masked from
+// klen / vlen inside VecTerms.
+__device__ __forceinline__ uint64_t digest_mix(
+    const DigestRec& c, bool konly, const uint8_t* __restrict__ spill,
+    const uint8_t* __restrict__ heap, uint32_t gl) {
+  const uint32_t kin = c.klen > (uint32_t)KEYW ? (uint32_t)KEYW : c.klen;
+  const uint32_t hv = konly ? 0 : c.vlen;
+  uint64_t acc = 0;
+  if (gl * 16 < kin)
+    acc += kbdigest::VecTerms(digest_u64(c.kv.x, c.kv.y), digest_u64(c.kv.z, c.kv.w),
+                              2 * gl, c.klen, kbdigest::SK);
+#pragma unroll
+  for (int t = 0; t < DIGEST_VR; ++t) {
+    const uint32_t v = gl + 16 * t;
+    if (v * 16 < hv)
+      acc += kbdigest::VecTerms(digest_u64(c.vv[t].x, c.vv[t].y),
+                                digest_u64(c.vv[t].z, c.vv[t].w), 2 * v, hv,
+                                kbdigest::SV);
+  }
+  const uint32_t nvec = (uint32_t)(((uint64_t)hv + 15) >> 4);
+  for (uint32_t v = gl + 16 * DIGEST_VR; v < nvec; v += 16) {
+    const u32x4 x = ((const u32x4*)(heap + c.vo))[v];
+    acc += kbdigest::VecTerms(digest_u64(x.x, x.y), digest_u64(x.z, x.w),
+                              2 * (uint64_t)v, hv, kbdigest::SV);
+  }
+  if (c.klen > (uint32_t)KEYW) {  // spill tail (keys > 96B): rare, loop
+    const uint32_t nt = (c.klen - (uint32_t)KEYW + 15) >> 4;
+    for (uint32_t t = gl; t < nt; t += 16) {
+      const u32x4 x = ((const u32x4*)(spill + c.ko))[t];
+      acc += kbdigest::VecTerms(digest_u64(x.x, x.y), digest_u64(x.z, x.w),
+                                12 + 2 * (uint64_t)t, c.klen, kbdigest::SK);
+    }
+  }
+  return acc;
+}
+
+__device__ __forceinline__ uint64_t digest_xor_sum(uint64_t v, int d) {
+  const uint32_t lo = __shfl_xor((uint32_t)v, d, 64);
+  const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
+  return v + digest_u64(lo, hi);
+}
+
+// fixed grid (sized by the CU count), blocks grid-stride over tile ids, the 4
+// waves take the 64-row slices of the tile round-robin. Per slice first
+// k_count_tiles' predicate (rev / meta / shadow 8-byte streams, the rev[i + 1]
+// load guarded by the end of the SEGMENT) as one ballot word. Then the wave
+// splits into four 16-lane groups; group g takes the slice's winners number
+// g, g + 4, ... in ballot order by stripping set bits. One group step is 16
+// lanes x one 16-byte vector = 256 B. The walk is software-pipelined: the
+// next winner's row words, key vectors and first value vectors are requested
+// (digest_load) before this winner's words go through the fmix chain
+// (digest_mix), so the loads of one record overlap the multiplies of the one
+// before it. Per record a 16-lane xor-shuffle sum of the lane terms, then
+// the group's lane 0 applies the finaliser and adds into its running sums.
+// Per tile: a wave reduction of the four sums, one LDS hop, four 64-bit
+// atomicAdds into the query's entry (integer sums commute: exact in any
+// order). A record with an unsafe source is skipped whole and counted, a
+// tile whose rows leave its run is skipped and not counted as done; the
+// host reports either as an error.
+__global__ __launch_bounds__(256) void k_digest_tiles(
+    Run b, int64_t n, Run d, int64_t dn, const uint64_t* __restrict__ shadow,
+    const uint8_t* __restrict__ spill, int64_t spill_used,
+    const uint8_t* __restrict__ heap, int64_t heap_used,
+    const DevRangeQ* __restrict__ qs, int nq,
+    const int64_t* __restrict__ bounds, const uint64_t* __restrict__ pfx,
+    int64_t T, int konly_i, uint64_t* __restrict__ dhdr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int grp = lane >> 4;
+  const uint32_t gl = (uint32_t)(lane & 15);
+  const bool konly = konly_i != 0;
+  const int nseg = 2 * nq;
+  __shared__ uint64_t wsum[4][4];
+  const uint64_t total = pfx[nseg];
+  uint64_t done = 0, rows_done = 0;  // thread 0's tallies of this block
+  for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {
+    const kbcount::Tile tl = kbcount::MapTile(bounds, pfx, nseg, t, T);
+    const bool isd = tl.run != 0;
+    const int64_t run_n = isd ? dn : n;
+    if (tl.r0 < 0 || tl.r0 >= tl.r1 || tl.r1 > tl.hi || tl.hi > run_n)
+      continue;  // block-uniform
+    const Run& r = isd ? d : b;
+    const uint64_t* __restrict__ rev = r.rev;
+    const uint64_t* __restrict__ meta = r.meta;
+    const uint64_t* __restrict__ sh = (!isd && dn > 0) ? shadow : nullptr;
+    const uint64_t R = qs[tl.query].read_rev;
+    const int64_t seg_hi = tl.hi;
+    uint64_t cnt = 0, kb = 0, vb = 0, hs = 0;  // sums of this lane's group
+    for (int64_t i0 = tl.r0 + ((int64_t)w << 6); i0 < tl.r1; i0 += 256) {
+      const int64_t i = i0 + lane;
+      bool win = false;
+      if (i < tl.r1) {
+        const uint64_t rv = rev[i], m = meta[i];
+        const uint64_t rvn = (i + 1 < seg_hi) ? rev[i + 1] : 0;
+        const uint64_t s = sh ? sh[i] : UINT64_MAX;
+        if (rv > 0 && rv <= R && !(m & M_TOMB) && !(s != UINT64_MAX && s <= R))
+          win = !(m & M_SAME_NEXT) || rvn > R;
+      }
+      uint64_t wins = __ballot(win);
+      for (int k = 0; k < grp; ++k) wins &= wins - 1;  // the groups before ours
+      DigestRec cur;
+      cur.state = 0;
+      if (wins)
+        digest_load(r, i0 + __builtin_ctzll(wins), konly, heap,
+                    (uint64_t)heap_used, (uint64_t)spill_used, gl, cur);
+      while (cur.state) {  // group-uniform
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wins &= wins - 1;  // our next: 4 further on
+        DigestRec nxt;
+        nxt.state = 0;
+        if (wins)
+          digest_load(r, i0 + __builtin_ctzll(wins), konly, heap,
+                      (uint64_t)heap_used, (uint64_t)spill_used, gl, nxt);
+        if (cur.state == 1) {
+          uint64_t acc = digest_mix(cur, konly, spill, heap, gl);
+#pragma unroll
+          for (int dd = 8; dd >= 1; dd >>= 1) acc = digest_xor_sum(acc, dd);
+          if (gl == 0) {
+            cnt += 1;
+            kb += cur.klen;
+            vb += cur.vlen;
+            hs += kbdigest::Finish(cur.rev, cur.klen, konly ? 0 : cur.vlen, acc, 0);
+          }
+        } else if (gl == 0) {
+          atomicAdd((unsigned long long*)&dhdr[4], 1ull);
+        }
+        cur = nxt;
+      }
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+      cnt = digest_xor_sum(cnt, dd);
+      kb = digest_xor_sum(kb, dd);
+      vb = digest_xor_sum(vb, dd);
+      hs = digest_xor_sum(hs, dd);
+    }
+    if (lane == 0) {
+      wsum[w][0] = cnt;
+      wsum[w][1] = kb;
+      wsum[w][2] = vb;
+      wsum[w][3] = hs;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long* e =
+          (unsigned long long*)&dhdr[DIGEST_HDR + 4 * (int64_t)tl.query];
+      if (wsum[0][0] + wsum[1][0] + wsum[2][0] + wsum[3][0]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          atomicAdd(&e[k], (unsigned long long)(wsum[0][k] + wsum[1][k] +
+                                                wsum[2][k] + wsum[3][k]));
+      }
+      done += 1;
+      rows_done += (uint64_t)(tl.r1 - tl.r0);
+    }
+    __syncthreads();  // wsum reused by the next tile
+  }
+  if (threadIdx.x == 0 && done) {
+    atomicAdd((unsigned long long*)&dhdr[0], (unsigned long long)done);
+    atomicAdd((unsigned long long*)&dhdr[1], (unsigned long long)rows_done);
+  }
+}
+
 // ---- batched watch registration: catch-up for many watchers --------------
 // (kb_watch_batch; watch.go:37-99 + Ring.FindEvents,
 // ring.go:84-118 per watcher). k_watch_catchup re-reads the ring span once
@@ -2975,6 +3252,51 @@ struct Slab::Impl {
     return true;
   }
 
+  // range digest (allocated on first use). As for the batched Count, every
+  // buffer is the call's own.
+  int64_t digest_tile = kbdigest::kDefaultTile;  // KB_DIGEST_TILE
+  int digest_grid = 1024;                        // CUs x 4 blocks (§3.11)
+  DevRangeQ *d_dq = nullptr, *h_dq = nullptr;
+  uint8_t* d_dtails = nullptr;
+  int64_t dtails_cap = 0;
+  int64_t* d_dbounds = nullptr;             // [4 * max_q]
+  uint64_t* d_dpfx = nullptr;               // [2 * max_q + 1]
+  uint64_t *d_dhdr = nullptr, *h_dhdr = nullptr;  // [DIGEST_HDR + 4 * max_q]
+  unsigned long long* d_dctr = nullptr;     // [2] k_range_bounds' counter pair
+  hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr, ev_d2 = nullptr;
+  void free_digest() {
+    for (void* q : {(void*)d_dq, (void*)d_dtails, (void*)d_dbounds,
+                    (void*)d_dpfx, (void*)d_dhdr, (void*)d_dctr})
+      if (q) (void)hipFree(q);
+    for (void* q : {(void*)h_dq, (void*)h_dhdr})
+      if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : {ev_d0, ev_d1, ev_d2})
+      if (e) (void)hipEventDestroy(e);
+  }
+  bool ensure_digest(int64_t tail_bytes, std::string* err) {
+    if (!d_dhdr) {
+      HIP_CHECK(hipEventCreate(&ev_d0));
+      HIP_CHECK(hipEventCreate(&ev_d1));
+      HIP_CHECK(hipEventCreate(&ev_d2));
+      HIP_CHECK(hipHostMalloc(&h_dq, (int64_t)max_q * sizeof(DevRangeQ)));
+      HIP_CHECK(hipHostMalloc(&h_dhdr, (int64_t)(DIGEST_HDR + 4 * max_q) * 8));
+      HIP_CHECK(hipMalloc(&d_dq, (int64_t)max_q * sizeof(DevRangeQ)));
+      HIP_CHECK(hipMalloc(&d_dbounds, (int64_t)max_q * 4 * 8));
+      HIP_CHECK(hipMalloc(&d_dpfx, (int64_t)(2 * max_q + 1) * 8));
+      HIP_CHECK(hipMalloc(&d_dctr, 16));
+      HIP_CHECK(hipMalloc(&d_dhdr, (int64_t)(DIGEST_HDR + 4 * max_q) * 8));
+    }
+    if (tail_bytes > dtails_cap || !d_dtails) {
+      if (d_dtails) (void)hipFree(d_dtails);
+      d_dtails = nullptr;
+      dtails_cap = 0;
+      int64_t cap = tail_bytes * 2 + 4096;
+      HIP_CHECK(hipMalloc(&d_dtails, cap));
+      dtails_cap = cap;
+    }
+    return true;
+  }
+
   // batched stream read (allocated once at Create, sized from
   // KB_STREAM_WINDOW, the delta capacity and KB_STREAM_MAX_KVS). Per run the
   // ballot words with their counts, bytes and prefixes (one word more than
@@ -3167,6 +3489,7 @@ struct Slab::Impl {
     free_list();
     free_getb();
     free_count();
+    free_digest();
     free_stream();
     if (h_pack) (void)hipHostFree(h_pack);
     for (int i = 0; i < 2; ++i) {
@@ -3423,6 +3746,7 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
   I->wreg_cfg_bytes = env_i64("KB_WATCH_REG_BYTES", kbwreg::kDefaultBytes);
   if (I->wreg_cfg_bytes < 8) I->wreg_cfg_bytes = 8;
   I->count_tile = kbcount::ClampTile(env_i64("KB_COUNT_TILE", kbcount::kDefaultTile));
+  I->digest_tile = kbcount::ClampTile(env_i64("KB_DIGEST_TILE", kbdigest::kDefaultTile));
   I->stream_window = kbstream::ClampWindow(
       env_i64("KB_STREAM_WINDOW", kbstream::kDefaultWindow));
   I->stream_max_kvs = kbstream::ClampMaxKvs(
@@ -3432,6 +3756,7 @@ Slab* Slab::Create(int64_t max_rows, int64_t heap_cap, int device,
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
                                 I->device);
     I->count_grid = (cus > 0 ? cus : 256) * 8;
+    I->digest_grid = (cus > 0 ? cus : 256) * 4;
   }
   std::string lerr;
   if (!err) err = &lerr;
@@ -4343,6 +4668,75 @@ bool Slab::CountBatchLaunch(const DevRangeQ* qs, int nq,
   perf.count_batch_launches++;
   perf.count_batch_tiles += (int64_t)h->tiles;
   perf.count_batch_rows += (int64_t)h->rows;
+  *hdr = h;
+  return true;
+}
+
+// ---- range digest (kb_digest_batch) ---------------------------------------
+
+int64_t Slab::digest_tile() const { return p->digest_tile; }
+
+bool Slab::DigestBatchLaunch(const DevRangeQ* qs, int nq,
+                             const std::string& qtails, bool keys_only,
+                             const DigestBatchHdr** hdr, std::string* err) {
+  Impl* I = p;
+  static_assert(sizeof(DigestBatchHdr) == (DIGEST_HDR + 4) * 8, "digest header");
+  if (nq <= 0 || nq > I->max_q) {
+    if (err) *err = "digest batch: bad sub-batch size (KB_MAX_Q)";
+    return false;
+  }
+  if (!I->ensure_digest((int64_t)qtails.size(), err)) return false;
+  memcpy(I->h_dq, qs, sizeof(DevRangeQ) * (size_t)nq);
+  HIP_CHECK(hipMemcpyAsync(I->d_dq, I->h_dq, sizeof(DevRangeQ) * (size_t)nq,
+                           hipMemcpyHostToDevice, I->stream));
+  if (!qtails.empty())
+    HIP_CHECK(hipMemcpyAsync(I->d_dtails, qtails.data(), qtails.size(),
+                             hipMemcpyHostToDevice, I->stream));
+  (void)hipGetLastError();  // drop stale sticky errors: check OUR launches
+  hipLaunchKernelGGL(k_range_bounds, dim3(nq), dim3(256), 0, I->stream,
+                     I->A.run(), I->n, I->DA.run(), I->dn, I->spillA,
+                     I->d_dtails, I->d_dq, nq, I->d_dbounds, I->d_dctr);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_d0, I->stream));
+  hipLaunchKernelGGL(k_digest_plan, dim3(1), dim3(256), 0, I->stream,
+                     I->d_dbounds, nq, I->digest_tile, I->d_dpfx, I->d_dhdr);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_digest_tiles, dim3((uint32_t)I->digest_grid), dim3(256),
+                     0, I->stream, I->A.run(), I->n, I->DA.run(), I->dn,
+                     I->shadow, I->spillA, I->spill_used_, I->heapA,
+                     I->heap_used_, I->d_dq, nq, I->d_dbounds, I->d_dpfx,
+                     I->digest_tile, keys_only ? 1 : 0, I->d_dhdr);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I->ev_d1, I->stream));
+  // the one small readback: five totals and 32 B per query
+  HIP_CHECK(hipMemcpyAsync(I->h_dhdr, I->d_dhdr,
+                           (int64_t)(DIGEST_HDR + 4 * nq) * 8,
+                           hipMemcpyDeviceToHost, I->stream));
+  HIP_CHECK(hipEventRecord(I->ev_d2, I->stream));
+  HIP_CHECK(hipStreamSynchronize(I->stream));
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_d0, I->ev_d1);
+  perf.digest_ms += ms;
+  ms = 0;
+  (void)hipEventElapsedTime(&ms, I->ev_d1, I->ev_d2);
+  perf.digest_d2h_ms += ms;
+  const DigestBatchHdr* h = (const DigestBatchHdr*)I->h_dhdr;
+  if (h->tiles != h->tiles_planned || h->rows != h->rows_planned) {
+    if (err) *err = "digest batch: the tile kernel did not cover the plan";
+    return false;
+  }
+  if (h->skipped) {
+    if (err) *err = "digest batch: a record's source is misaligned or leaves its heap";
+    return false;
+  }
+  perf.digest_batch_launches++;
+  perf.digest_batch_tiles += (int64_t)h->tiles;
+  perf.digest_batch_rows += (int64_t)h->rows;
+  for (int q = 0; q < nq; ++q) {
+    perf.digest_batch_kvs += (int64_t)h->e[q].count;
+    perf.digest_batch_bytes +=
+        (int64_t)(h->e[q].key_bytes + (keys_only ? 0 : h->e[q].value_bytes));
+  }
   *hdr = h;
   return true;
 }

@@ -147,6 +147,14 @@ struct Perf {
   double count_ms = 0, count_d2h_ms = 0;
   int64_t count_batch_calls = 0, count_batch_q = 0, count_batch_launches = 0,
           count_batch_tiles = 0, count_batch_rows = 0;
+  // range digest (kb_digest_batch): k_digest_plan + k_digest_tiles kernel
+  // time, the header D2H, queries the kernels served, launches, tiles and
+  // rows covered, winners hashed and the key + value bytes that went through
+  // the hash
+  double digest_ms = 0, digest_d2h_ms = 0;
+  int64_t digest_batch_calls = 0, digest_batch_q = 0, digest_batch_launches = 0,
+          digest_batch_tiles = 0, digest_batch_rows = 0, digest_batch_kvs = 0,
+          digest_batch_bytes = 0;
   // batched stream read (kb_stream_next_batch): time in the k_stream_*
   // kernels, the header and reply D2H, calls, windows scanned, rows the mark
   // kernel covered, kvs returned, records served by the host fallback
@@ -209,6 +217,17 @@ struct CountBatchHdr {
   uint64_t tiles, rows, tiles_planned, rows_planned;
   uint64_t count[1];  // nq entries
 };
+// range digest (kb_digest_batch): what k_digest_plan and
+// k_digest_tiles leave per launch. skipped = winners whose key tail or value
+// was not safely readable; it must be zero.
+struct DigestEntry {
+  uint64_t count, key_bytes, value_bytes, hash;
+};
+struct DigestBatchHdr {
+  uint64_t tiles, rows, tiles_planned, rows_planned, skipped;
+  DigestEntry e[1];  // nq entries
+};
+static_assert(sizeof(DigestEntry) == 32, "digest entry layout");
 // batched stream read (kb_stream_next_batch): what
 // k_stream_plan leaves per window and k_stream_cut / k_stream_emit per call
 struct StreamWinHdr {
@@ -416,6 +435,18 @@ class Slab {
   bool CountBatchLaunch(const DevRangeQ* qs, int nq, const std::string& qtails,
                         const CountBatchHdr** hdr, std::string* err);
   int64_t count_tile() const;  // KB_COUNT_TILE: rows per tile
+
+  // range digest (kb_digest_batch). DigestBatchLaunch takes
+  // what CountBatchLaunch takes and runs k_range_bounds, k_digest_plan and
+  // k_digest_tiles back to back on buffers of its own, then reads back the
+  // totals and 32 B per query; *hdr points into pinned memory valid until the
+  // next call. Reads the key columns, the key-spill heap and (unless
+  // keys_only) the value heap; writes neither the winner tables nor the
+  // arena nor the range counters. Fails if a winner's source was unsafe.
+  bool DigestBatchLaunch(const DevRangeQ* qs, int nq, const std::string& qtails,
+                         bool keys_only, const DigestBatchHdr** hdr,
+                         std::string* err);
+  int64_t digest_tile() const;  // KB_DIGEST_TILE: rows per tile
 
   // batched stream read (kb_stream_next_batch).
   // StreamWindowLaunch scans one window: k_stream_window (cont = false: from

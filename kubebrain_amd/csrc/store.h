@@ -99,6 +99,15 @@ class Store {
   Status CountBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
                     size_t cap, size_t* out_len, uint64_t* total_count,
                     std::string* err = nullptr);
+  // range digest (kb_digest_batch): per range the count, key bytes, value
+  // bytes and hash sum of the kvs an unbounded List returns, reduced across
+  // the chip; qbuf as for CountBatch, reply = u32 n; n x
+  // {i32 status; i32 0; u64 header_rev; u64 count; u64 key_bytes; u64
+  // value_bytes; u64 hash}. flags bit 0 = keys_only. NOBUF writes nothing
+  // (*out_len = required size).
+  Status DigestBatch(const uint8_t* qbuf, size_t n, int flags, uint8_t* out,
+                     size_t cap, size_t* out_len, uint64_t* total_kvs,
+                     std::string* err = nullptr);
   uint64_t Compact(uint64_t revision, Status* st);
   uint64_t GetCurrentRevision();
   void SetCurrentRevision(uint64_t rev);
